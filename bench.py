@@ -16,13 +16,17 @@ Default workload = BASELINE.json configs[1]: 40 views x 256 ch, 40x40x16 voxels.
 
 Multi-GPU: scenes are independent (batch size is 1 scene per GPU in the reference too), so
 ranks shard scenes with NO data-path collective; scaling is weak (one scene per rank per
-step).  Rank 0 prints ONE JSON line; ``roofline`` is for the deformable-gather kernel at the
+step).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times --steps steps and prints the headline line; ``--dump-outputs DIR``
+also writes what the last timed step computed as DIR/<name>.npy.  Everything else runs only with
+``--full`` (its fields are then in the same line): ``roofline`` is for the deformable-gather kernel at the
 finest level, timed with HIP events on its launch stream (with the default whole-scene hipGraph
 replay the events bracket the same kernel in an eager pass over the same scenes right after the
 timed region -- ``roofline.measured`` says which), ``roofline_mfma`` for the 90-GFLOP convolution, ``path_roofline`` for the whole path against its composite floor,
 ``cpu_baseline`` is the CPU oracle (a port: the reference has no CPU implementation of this path)
 on a bounded sample on the host cores, ``self_check`` re-runs the scenes-in-flight configuration
-against serial eager launches bit for bit.
+against serial eager launches bit for bit; ``strict_fp32`` and ``sustained`` are extra timed legs.
 """
 import argparse
 import json
@@ -104,7 +108,18 @@ def parse():
                          "as-timed = the geometry of the timed region (with scenes in flight: the throughput geometry, which sizes "
                          "the layers with few voxels for CU-time, not for their own latency), latency = every kernel alone at its "
                          "latency-optimal split (what a per-layer table of kernel-alone times should be read with)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline does not need: the sustained and strict-fp32 legs, the "
+                         "eager pass behind the roofline objects (and --breakdown), the self check and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned to its callers as DIR/<name>.npy (float32 / float64, at "
+                         "most 60 MiB in all: beyond that the largest arrays are cut to a fixed seeded sample)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.breakdown and not args.full:
+        ap.error("--breakdown reads the eager pass of --full")
+    return args
 
 
 def build_path(w, device):
@@ -238,6 +253,43 @@ def cpu_baseline(w, n_views, seed):
         out["one_thread" if runs[1]["cores"] == 1 else "all_cores"] = {k: v for k, v in runs[1].items() if k != "kind"}
     set_threads(all_cores)
     return out
+
+
+DUMP_BYTES = 60 * 2 ** 20      # --dump-outputs writes at most this much (< 64 MB), .npy headers included
+
+
+def dump_outputs(out_dir, results):
+    """--dump-outputs: what the callers of the timed path received from its last step -- one dict per scene of the batch
+    (volume, valid, occ and the head lists, as ``forward_features`` returns them) -- as ``s<k>_<key>[_<level>].npy``:
+    floating and bool tensors in float32 (float64 stays float64), integer ones in float64 (exact).  Arrays are kept whole,
+    smallest first, while they fit the even share of what is left of DUMP_BYTES; a larger one is cut to a sample of its
+    flattened elements at seeded random positions (ascending), written 1-D.  The sample depends on the shapes only, so two
+    runs with the same arguments write the same positions.  Returns a summary for the JSON line."""
+    import numpy as np
+    arrays = []
+    for k, r in enumerate(results):
+        for key in sorted(r):
+            v = r[key]
+            for name, t in ([(f"s{k}_{key}", v)] if torch.is_tensor(v) else [(f"s{k}_{key}_{j}", t) for j, t in enumerate(v)]):
+                dt = torch.float64 if t.dtype == torch.float64 or not (t.is_floating_point() or t.dtype == torch.bool) else torch.float32
+                arrays.append((name, t, dt))
+    header = 128                                        # bytes of one .npy header (numpy pads it to a multiple of 64)
+    left, n_left = DUMP_BYTES - header * len(arrays), len(arrays)
+    os.makedirs(out_dir, exist_ok=True)
+    sampled, total = [], 0
+    for name, t, dt in sorted(arrays, key=lambda a: a[1].numel() * a[2].itemsize):
+        take = min(t.numel(), left // n_left // dt.itemsize)
+        if take < t.numel():
+            pos = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(t.numel())).narrow(0, 0, take).sort().values
+            a = t.reshape(-1)[pos.to(t.device)].to(dt).cpu().numpy()
+            sampled.append(f"{name}: {take} of {t.numel()} elements")
+        else:
+            a = t.to(dt).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+        n_left -= 1
+        total += a.nbytes + header
+    return dict(arrays=len(arrays), bytes=total, sampled=sampled)
 
 
 def launch_ranks(args):
@@ -374,9 +426,12 @@ def main():
     # host-side events, and with several scenes in flight an event bracket on one stream also holds the time the kernel waits
     # for CUs the other scenes occupy (round 3's strict-fp32 line read 855 us for a 92-us gather that way).  They are taken in a
     # separate eager pass, one scene at a time, right after the timed region.
+    last_step = []                        # what the last step returned, one result dict per scene (--dump-outputs)
     t0 = time.perf_counter()
     for i in range(n_timed):              # args.steps batches of spp scenes, batch k = scenes k * spp .. k * spp + spp - 1
-        step(i)
+        r = step(i)
+        if i >= n_timed - spp:
+            last_step.append(r)
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
@@ -384,10 +439,12 @@ def main():
     elapsed = time.perf_counter() - t0
     log, ops.event_log = ops.event_log, None
     elapsed = sgc_dist.max_over_ranks(elapsed, device=device)
+    # before anything replays the graphs whose output buffers these are
+    dumped = dump_outputs(args.dump_outputs, last_step) if args.dump_outputs and rank == 0 else None
     # ---- sustained leg (untimed for `value`): the same configuration for >= 2 s, so that DVFS shows (a 50 ms burst of
     #      bf16 MFMA work runs at boost clocks) ----
     sustained = None
-    if args.sustain > 0:
+    if args.full and args.sustain > 0:
         n_sus = max(n_timed, int(args.sustain / max(elapsed / n_timed, 1e-6)) + 1)
         if dist is not None:
             dist.barrier()
@@ -403,23 +460,25 @@ def main():
                          ms_per_scene=round(el_s / n_sus * 1e3, 3))
     # same scenes, same kernels launched eagerly right after the timed region, one scene at a time: the deformable
     # gather is bracketed by HIP events on its launch stream (its pair count comes back to the host here)
-    scene_graph_was, det.scene_graph = det.scene_graph, False
-    tail_graph, det.use_graph = det.use_graph, False        # events cannot be recorded inside a capture / replay
-    if args.eager_geometry == "latency":
-        set_throughput_mode(False, keep_winograd=True)   # the splits of the latency geometry, the SAME convolution forms as the timed graphs
-    ops.event_log = []
-    ops.event_names = None if args.breakdown else PATH_KERNELS
-    calls0 = ops.n_calls
-    with torch.no_grad():
-        for i in range(max(6, min(n_timed, 20))):         # one scene at a time: the kernel on its own
-            feats, dpt, metas = scenes[i % n_scenes]
-            det.forward_features(feats, metas, dpt)
-            torch.cuda.synchronize()
-    log, ops.event_log = ops.event_log, None
-    lib_calls_per_scene = (ops.n_calls - calls0) / max(6, min(n_timed, 20))
-    det.scene_graph, det.use_graph = scene_graph_was, tail_graph
-    if args.eager_geometry == "latency":
-        set_throughput_mode(args.streams > 1, keep_winograd=True)   # back to the geometry the graphs were captured with (the self check compares bits)
+    log = []
+    if args.full:
+        scene_graph_was, det.scene_graph = det.scene_graph, False
+        tail_graph, det.use_graph = det.use_graph, False        # events cannot be recorded inside a capture / replay
+        if args.eager_geometry == "latency":
+            set_throughput_mode(False, keep_winograd=True)   # the splits of the latency geometry, the SAME convolution forms as the timed graphs
+        ops.event_log = []
+        ops.event_names = None if args.breakdown else PATH_KERNELS
+        calls0 = ops.n_calls
+        with torch.no_grad():
+            for i in range(max(6, min(n_timed, 20))):         # one scene at a time: the kernel on its own
+                feats, dpt, metas = scenes[i % n_scenes]
+                det.forward_features(feats, metas, dpt)
+                torch.cuda.synchronize()
+        log, ops.event_log = ops.event_log, None
+        lib_calls_per_scene = (ops.n_calls - calls0) / max(6, min(n_timed, 20))
+        det.scene_graph, det.use_graph = scene_graph_was, tail_graph
+        if args.eager_geometry == "latency":
+            set_throughput_mode(args.streams > 1, keep_winograd=True)   # back to the geometry the graphs were captured with (the self check compares bits)
     roofline_pass = ("HIP events on the launch stream in an eager pass over the same scenes, one scene at a time, right "
                      "after the timed region (the timed region replays hipGraphs, which cannot carry events, with several "
                      "scenes in flight; inside it the kernel shares the chip with the other scenes and runs 0-3 % longer, see "
@@ -427,7 +486,7 @@ def main():
 
     # ---- self check (untimed): the scenes-in-flight configuration reproduces the serial, graph-free results ----
     self_check = None
-    if rank == 0:
+    if args.full and rank == 0:
         graph_was = det.use_graph, det.scene_graph
         det.use_graph = det.scene_graph = False
         with torch.no_grad():
@@ -616,7 +675,7 @@ def main():
     # ---- strict-fp32 leg: the same scenes with exact fp32 products on the fp32 MFMA (--conv-mode f32), so that the
     #      bf16x3 headline never hides what IEEE-fp32 arithmetic costs ----
     strict = None
-    if args.conv_mode == "bf16x3" and not args.no_strict_fp32:
+    if args.full and args.conv_mode == "bf16x3" and not args.no_strict_fp32:
         set_conv_mode("f32")
         sg, ug = det.scene_graph, det.use_graph
         det.scene_graph, det.use_graph = False, True        # eager view transform + hipGraph tail (no device-count GEMMs in f32)
@@ -640,7 +699,7 @@ def main():
         det.scene_graph, det.use_graph = sg, ug
 
     tail_stats = None
-    if rank == 0 and (det.masked_tail or args.occupancy != "predicted"):
+    if args.full and rank == 0 and (det.masked_tail or args.occupancy != "predicted"):
         # what the output masks of the decoder tail keep alive on the last scene (tools/valid_stats.py prints more): fractions of
         # voxels in valid / dilate(valid) / dilate^2(valid) and of the halo kernel's 256-voxel bricks holding one such voxel
         import torch.nn.functional as F
@@ -702,14 +761,14 @@ def main():
                                   "none": "eager"}[args.graph],
                        "sharding": "scenes across ranks, no collective",
                        "library_calls_per_scene": lib_calls_per_scene},
-            "roofline": roofline,
-            "roofline_mfma": roofline_mfma,
-            "path_roofline": path_roofline,
-            "strict_fp32": strict,
-            "sustained": sustained,
-            "self_check": self_check,
+            "full": args.full,
         }
-        if not args.no_cpu_baseline and world == 1:
+        if dumped is not None:
+            out["dump_outputs"] = dumped
+        if args.full:
+            out.update(roofline=roofline, roofline_mfma=roofline_mfma, path_roofline=path_roofline, strict_fp32=strict,
+                       sustained=sustained, self_check=self_check)
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 out["cpu_baseline"] = cpu_baseline(w, n_views, seed=0)
             except Exception as e:  # the baseline is reported, never required for the GPU number

@@ -60,22 +60,30 @@ def test_product_never_imports_the_oracle():
                 assert not re.search(r"^\s*(import|from)\s+oracle\b", src, flags=re.M), os.path.join(dirpath, f)
 
 
-REF_CONFIGS = "/root/reference/configs"
+# the `model` settings of the reference's four configs, as Config.fromfile reads them (tests/golden/make_golden_configs.py)
+REF_CONFIGS = os.path.join(ROOT, "tests", "golden", "ref_configs.json")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CONFIGS), reason="reference tree only exists in the build container")
+def _ref_model_cfg(name):
+    import json
+    from sgcdet_amd.mmcv_lite import _wrap
+    with open(REF_CONFIGS) as f:
+        model = json.load(f, object_hook=lambda d: tuple(d["__tuple__"]) if set(d) == {"__tuple__"} else d)[name]
+    return _wrap(model)
+
+
 @pytest.mark.parametrize("name,params_m,depth_m", [("SGCDet_ScanNet", 79.75, 14.03), ("SGCDet_ARKit", 79.74, 14.03),
                                                    ("SGCDet_large_ScanNet200", 22.17, 13.88), ("SGCDet_large_ARKit", 21.58, 13.88)])
 def test_reference_configs_build_unchanged(name, params_m, depth_m):
     import sgcdet_amd.plugin  # noqa: F401
-    from sgcdet_amd.mmcv_lite import Config, build_detector
-    cfg = Config.fromfile(os.path.join(REF_CONFIGS, name + ".py"))
-    det = build_detector(cfg.model)
+    from sgcdet_amd.mmcv_lite import build_detector
+    model = _ref_model_cfg(name)
+    det = build_detector(model)
     nd = sum(p.numel() for p in det.depth_head.parameters()) / 1e6          # DepthNet_Fusion (f-2) is built from the config too
     nf = sum(p.numel() for p in det.neck.parameters()) / 1e6                # and the image FPN (f-1): 4 lateral 1x1 + 4 output 3x3
     n = sum(p.numel() for p in det.parameters()) / 1e6 - nd - nf            # voxel head + neck + head
     assert abs(n - params_m) < 0.02 and abs(nd - depth_m) < 0.02, (n, nd)
-    c = cfg.model["neck"]["out_channels"]
+    c = model["neck"]["out_channels"]
     assert sum(p.numel() for p in det.neck.parameters()) == sum(ci * c + c for ci in (256, 512, 1024, 2048)) + 4 * (9 * c * c + c)
     keys = det.state_dict().keys()
     for k in ("neck.lateral_convs.3.conv.weight", "neck.fpn_convs.0.conv.bias","voxel_head.base_heads.0.ref_3d",
