@@ -2,8 +2,11 @@
 
 One table drives every binding of that header: the product library
 (``sgcdet_amd/csrc/libsgcdet_amd.so``, HIP/gfx950) and -- from the test side
-only -- the CPU oracle that exports the same symbols.  Nothing here touches
-torch; pointers are plain integers (``tensor.data_ptr()``).
+only -- the CPU oracle that exports the same symbols.  The training-only entry
+points of ``include/sgcdet_amd_train.h`` have a table of their own
+(``TRAIN_SIGNATURES`` / ``TRAIN_INTROSPECTION``), bound only when ``Library`` is
+asked for it (the product library; the oracle has no twin of them).  Nothing
+here touches torch; pointers are plain integers (``tensor.data_ptr()``).
 """
 import ctypes as C
 
@@ -95,6 +98,15 @@ INTROSPECTION = {
     "sgc_pairs_geometry_linear_workspace_bytes": (C.c_int64, [_i]),
 }
 
+# include/sgcdet_amd_train.h: training-only entry points (no CPU-oracle twin)
+TRAIN_SIGNATURES = {
+    "sgc_plane_sweep_corr_backward": [_p] * 7 + [C.c_int64] + [_i] * 6 + [_p],
+}
+
+TRAIN_INTROSPECTION = {
+    "sgc_plane_sweep_corr_backward_workspace_bytes": (C.c_int64, [_i] * 5),
+}
+
 ABI_VERSION = 4      # == SGC_ABI_VERSION of include/sgcdet_amd.h (tests/test_abi_cpu.py compares the two)
 
 
@@ -105,11 +117,14 @@ class SgcError(RuntimeError):
 class Library:
     """A loaded shared object exporting the sgcdet_amd C ABI."""
 
-    def __init__(self, path):
+    def __init__(self, path, train=False):
+        """``train``: also bind (and require) the entry points of include/sgcdet_amd_train.h."""
         self.path = str(path)
         self._dll = C.CDLL(self.path)
         missing = []
-        for name, argtypes in SIGNATURES.items():
+        signatures = {**SIGNATURES, **TRAIN_SIGNATURES} if train else SIGNATURES
+        introspection = {**INTROSPECTION, **TRAIN_INTROSPECTION} if train else INTROSPECTION
+        for name, argtypes in signatures.items():
             try:
                 fn = getattr(self._dll, name)
             except AttributeError:
@@ -117,7 +132,7 @@ class Library:
                 continue
             fn.argtypes = argtypes
             fn.restype = C.c_int
-        for name, (res, argtypes) in INTROSPECTION.items():
+        for name, (res, argtypes) in introspection.items():
             try:
                 fn = getattr(self._dll, name)
             except AttributeError:

@@ -293,6 +293,29 @@ class NchwToRowsFunction(Function):
         return ext.ops().nhwc_to_nchw_pad(grad_rows.float().contiguous(), h, w)
 
 
+class PlaneSweepCorrFunction(Function):
+    """Plane-sweep matching cost of ``DepthNet_Fusion`` (depth_est_fusion.py homo_warping :87-126 + the cost-volume loop
+    :233-240) with its gradient on the HIP kernels: forward ``sgc_plane_sweep_corr``, backward
+    ``sgc_plane_sweep_corr_backward`` (include/sgcdet_amd_train.h).  rows [N, H*W, C] channels-last matching features
+    (the only differentiable input: the reference builds the sampling grid under no_grad), nbr [N,K] int32,
+    rt [N,K,12], depth [D] -> corr [N,D,H,W].  Saves only its inputs: no warped [N,C,D,H,W] tensor exists."""
+
+    @staticmethod
+    def forward(ctx, rows, nbr, rt, depth, H, W):
+        rows = rows.detach()
+        ctx.hw = (H, W)
+        ctx.save_for_backward(rows, nbr, rt, depth)
+        return ext.ops().plane_sweep_corr(rows, nbr, rt, depth, H, W)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_corr):
+        rows, nbr, rt, depth = ctx.saved_tensors
+        H, W = ctx.hw
+        grad_rows = ext.ops().plane_sweep_corr_backward(rows, nbr, rt, depth, grad_corr.float().contiguous(), H, W)
+        return grad_rows, None, None, None, None, None
+
+
 def _pad_cols(t, mult):
     """[rows, C] -> [rows, ceil(C / mult) * mult] with zero columns (a view when nothing is added)."""
     c = t.shape[-1]

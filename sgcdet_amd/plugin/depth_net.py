@@ -9,10 +9,14 @@ BatchNorm registered twice, exactly as in the reference).
 
 What differs on MI355X: in inference the plane-sweep cost volume (homography warp of the K neighbour views at D depth
 planes + correlation, :229-240) is ONE fused HIP kernel (``sgc_plane_sweep_corr``, csrc/plane_sweep.hip) -- the warped
-features [N, C, D, H, W] (1.18 GB per neighbour at config 2) never exist.  With autograd enabled the reference's
-``F.grid_sample`` formulation runs (differentiable, same numbers).  The 2-D convolutions are library convolutions
+features [N, C, D, H, W] (1.18 GB per neighbour at config 2) never exist.  With autograd enabled the same kernel runs
+forward and its gradient comes from ``sgc_plane_sweep_corr_backward`` (csrc/plane_sweep_bwd.hip);
+``SGC_PLANE_SWEEP_FUSED_GRAD=0`` restores the reference's ``F.grid_sample`` formulation under autograd (A/B runs).  On
+the CPU the reference formulation runs.  The 2-D convolutions are library convolutions
 (MIOpen through torch): dense 2-D CNNs are not part of the hot path.
 """
+import os
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -187,7 +191,8 @@ class DepthNet_Fusion(nn.Module):
         """Plane-sweep matching cost [N, D, H, W] of the N views against their time-adjacent neighbours (:219-240)."""
         num_src, channel_num, H, W = f_mvs.shape
         k = min(self.neighbor_img_num, num_src - 1)
-        if f_mvs.is_cuda and not (torch.is_grad_enabled() and f_mvs.requires_grad):
+        needs_grad = torch.is_grad_enabled() and f_mvs.requires_grad
+        if f_mvs.is_cuda and not (needs_grad and os.environ.get("SGC_PLANE_SWEEP_FUSED_GRAD", "1") == "0"):
             return plane_sweep_correlation(f_mvs, img_meta, stride, self.depth_values, self.neighbor_img_num)
         dev = f_mvs.device
         src_w2c = torch.tensor(np.array(img_meta["lidar2img"]["extrinsic"]), device=dev)

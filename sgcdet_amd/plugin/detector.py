@@ -261,6 +261,20 @@ class SGCDet(nn.Module):
             losses.update(self.voxel_head.occ_loss(occ, sem_occ, geo_occ))
         return losses
 
+    def forward_train_from_fpn(self, x, img, img_metas, gt_bboxes_3d, gt_labels_3d, depth_maps=None):
+        """SGCDet.forward_train (SGCDet.py:98-114) from the FPN maps and the images on, depth head included: the depth
+        distribution of ``depth_head`` (SGCDet.py:75-82: ``x[0]`` is detached only with ``depth_loss``; ``use_gt_dpt``
+        takes the ground-truth bins instead), ``loss_dpt`` from ``DepthNet_Fusion.loss`` when ``depth_loss=True``
+        (:108-109), then exactly ``forward_train_from_features``.  x = FPN maps [B,N,C,H_l,W_l], img [B,N,3,4H,4W],
+        depth_maps [B,N,4H,4W] (needed with ``use_gt_dpt`` or ``depth_loss``)."""
+        if (self.use_gt_dpt or self.depth_loss) and depth_maps is None:
+            raise RuntimeError("SGCDet.forward_train_from_fpn: use_gt_dpt / depth_loss need depth_maps")
+        dpt_dist = self.depth_distribution(x, img, img_metas, depth_maps)
+        losses = self.forward_train_from_features(x, img_metas, dpt_dist, gt_bboxes_3d, gt_labels_3d)
+        if self.depth_loss:
+            losses.update(self.depth_head.loss(depth_maps, dpt_dist))
+        return losses
+
     def simple_test_from_features(self, x, img_metas, dpt_dist, as_results=False):
         """SGCDet.simple_test (SGCDet.py:119-129) from the FPN maps on.  ``as_results=True`` returns the reference's
         ``bbox3d2result`` dicts (mmdet3d core/bbox/transforms.py:50-77: ``boxes_3d`` / ``scores_3d`` / ``labels_3d`` on

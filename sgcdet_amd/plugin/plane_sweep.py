@@ -6,12 +6,14 @@ Reference: mmdet3d_plugin/models/im2voxel/depth_utils/depth_est_fusion.py -- ``g
 (:203-240).  The 2-D CNNs around it (``ResNetFPN``, ``SimpleUnet2D``) are dense library convolutions and are not
 built here.  ``plane_sweep_correlation`` takes what ``forward`` has at :222 (matching features + ``img_meta``) and
 returns what it has at :240 (``correlation``), computed by ``sgc_plane_sweep_corr`` without materialising the warped
-neighbour features [N, C, D, H, W].
+neighbour features [N, C, D, H, W].  Under autograd the same call is differentiable with respect to the matching
+features (``functions.PlaneSweepCorrFunction``: backward ``sgc_plane_sweep_corr_backward``).
 """
 import numpy as np
 import torch
 
 from .. import ext
+from ..functions import NchwToRowsFunction, PlaneSweepCorrFunction
 
 
 def closest_frame_ids(num_cams, num_select):
@@ -41,7 +43,8 @@ def relative_projections(w2c, intrinsic, neighbor_ids):
 def plane_sweep_correlation(f_mvs, img_meta, stride, depth_values, neighbor_img_num=2):
     """f_mvs [N, C, H, W] matching features of the N views (any memory format); ``stride`` = image / feature
     resolution ratio used for the intrinsics (:209-213); depth_values [D] plane depths (:179).
-    Returns correlation [N, D, H, W] (:240)."""
+    Returns correlation [N, D, H, W] (:240); differentiable with respect to ``f_mvs`` (the gradient arrives in the
+    caller's memory format)."""
     N, C, H, W = f_mvs.shape
     dev = f_mvs.device
     ops = ext.ops() if f_mvs.is_cuda else None
@@ -57,10 +60,16 @@ def plane_sweep_correlation(f_mvs, img_meta, stride, depth_values, neighbor_img_
     k = min(neighbor_img_num, N - 1)
     nbr = closest_frame_ids(N, k)
     rt = relative_projections(w2c, intr, nbr).reshape(N, k, 12).contiguous().to(dev)
+    depth = torch.as_tensor(depth_values, dtype=torch.float32).to(dev).contiguous()
+    nbr = nbr.to(torch.int32).to(dev).contiguous()
+    grad = torch.is_grad_enabled() and f_mvs.requires_grad
     # channels-last rows: zero-copy when the extractor already writes channels-last, one transpose launch otherwise
     if f_mvs.is_contiguous(memory_format=torch.channels_last) and f_mvs.dtype == torch.float32:
         rows = f_mvs.permute(0, 2, 3, 1).reshape(N, H * W, C)
+    elif grad:
+        rows = NchwToRowsFunction.apply(f_mvs)         # its backward hands a contiguous NCHW gradient back
     else:
         rows = ops.nchw_to_nhwc_crop(f_mvs.float().contiguous(), H, W)
-    depth = torch.as_tensor(depth_values, dtype=torch.float32).to(dev).contiguous()
-    return ops.plane_sweep_corr(rows, nbr.to(torch.int32).to(dev).contiguous(), rt, depth, H, W)
+    if grad:
+        return PlaneSweepCorrFunction.apply(rows, nbr, rt, depth, H, W)
+    return ops.plane_sweep_corr(rows, nbr, rt, depth, H, W)

@@ -1084,6 +1084,24 @@ class TensorOps:
         self._call("sgc_plane_sweep_corr", feat, nbr, rt, depth, corr, N, K, H, W, Cc, D)
         return corr
 
+    def plane_sweep_corr_backward(self, feat, nbr, rt, depth, grad_corr, H, W):
+        """Gradient of ``plane_sweep_corr`` with respect to ``feat`` (include/sgcdet_amd_train.h): the same inputs plus
+        grad_corr [N,D,H,W] -> grad_feat [N, H*W, C] (both roles of the features, fully written)."""
+        self._check(feat=feat, nbr=nbr, rt=rt, depth=depth, grad_corr=grad_corr)
+        self._f32(feat=feat, rt=rt, depth=depth, grad_corr=grad_corr)
+        self._i32(nbr=nbr)
+        N, S, Cc = feat.shape
+        K = nbr.shape[1]
+        D = depth.numel()
+        if S != H * W or nbr.shape != (N, K) or rt.shape != (N, K, 12) or grad_corr.shape != (N, D, H, W):
+            raise RuntimeError("plane_sweep_corr_backward: inconsistent shapes")
+        nbytes = int(self.lib._dll.sgc_plane_sweep_corr_backward_workspace_bytes(N, K, H, W, D))
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=feat.device)
+        grad_feat = torch.empty_like(feat)
+        self._call("sgc_plane_sweep_corr_backward", feat, nbr, rt, depth, grad_corr, grad_feat, ws, nbytes,
+                   N, K, H, W, Cc, D)
+        return grad_feat
+
     def conv3d_cl(self, x, wt, grid, ksize, stride=1, transposed=False, scale=None, shift=None,
                   residual=None, relu=False):
         """x [X*Y*Z, Cin] channels-last; wt [taps, Cout, Cin]; grid = (X, Y, Z) of the input;
