@@ -43,6 +43,57 @@ int sgc_plane_sweep_corr_backward(const float *feat, const int32_t *nbr, const f
                                   int N, int K, int H, int W, int C, int D, sgc_stream_t stream);
 int64_t sgc_plane_sweep_corr_backward_workspace_bytes(int N, int K, int H, int W, int D);
 
+/* ------------------------------------------------------------------------- *
+ * 10. The parameter update: global-norm gradient clipping + AdamW over a list of tensors (csrc/optim.hip)
+ * ------------------------------------------------------------------------- */
+
+/* Both calls walk a list of items in DEVICE memory, one per parameter tensor that has a gradient this step (the pattern of
+ * sgc_pack_item): block_start ascending from 0, item i owning ceil(numel / block_elems) workgroups, total_blocks = their sum.
+ * All four tensors are dense fp32 of numel elements (the raw pointers carry no type: a caller that holds anything else must
+ * refuse it -- sgcdet_amd.optim raises TypeError); tensors that are not 16-byte aligned take a scalar path.
+ *   step                    this tensor's own count of updates AFTER this one (torch's state["step"]; a parameter without a
+ *                           gradient in some steps lags the others);
+ *   bias_correction1        1 - beta1^step, bias_correction2_sqrt = sqrt(1 - beta2^step): computed by the host in double
+ *                           as torch computes them, rounded to fp32;
+ *   block_elems             elements per workgroup of this item, a positive multiple of 4 (a block whose item says otherwise
+ *                           does nothing). */
+typedef struct sgc_optim_item {
+  float *param;
+  const float *grad;
+  float *exp_avg, *exp_avg_sq;
+  int64_t numel;
+  int32_t group, step, block_start, block_elems;
+  float bias_correction1, bias_correction2_sqrt;
+} sgc_optim_item;                 /* 64 bytes */
+
+/* Hyper-parameters of one parameter group, as torch holds them (Python floats). */
+typedef struct sgc_optim_group {
+  double lr, weight_decay, beta1, beta2, eps;
+} sgc_optim_group;                /* 40 bytes */
+#define SGC_OPTIM_MAX_GROUPS 8
+
+/* norm_out[0] = sqrt(sum of grad^2 over every item) == the total_norm of torch.nn.utils.clip_grad_norm_(norm_type = 2).
+ * Two launches: one fp32 partial per workgroup (plain stores), then one wave adds the partials in index order in fp64.
+ * No float atomics: bitwise reproducible run to run for a given item list.
+ *   partials: >= sgc_grad_sqnorm_batch_workspace_bytes(total_blocks) bytes, contents irrelevant;  norm_out: 1 float (device). */
+int sgc_grad_sqnorm_batch(const void *items, int n_items, int total_blocks, float *partials, float *norm_out,
+                          sgc_stream_t stream);
+int64_t sgc_grad_sqnorm_batch_workspace_bytes(int total_blocks);
+
+/* One AdamW step (torch.optim.AdamW, amsgrad = False, maximize = False, fp32) of every item in ONE launch, per element:
+ *   c = min(1, max_norm / (norm[0] + 1e-6))          (max_norm <= 0 or norm == NULL: c = 1, no clipping)
+ *   g = grad * c                                     (registers only: grad is NOT written)
+ *   p = p * (1 - lr * weight_decay)
+ *   m = m + (g - m) * (1 - beta1)
+ *   v = v * beta2 + (1 - beta2) * g * g
+ *   p = p - (lr / bias_correction1) * (m / (sqrt(v) / bias_correction2_sqrt + eps))
+ *   groups: n_groups <= SGC_OPTIM_MAX_GROUPS structs in HOST memory, copied into the kernel's arguments (no device copy of
+ *   what a scheduler changes every step);  norm: 1 float in DEVICE memory (sgc_grad_sqnorm_batch's norm_out), read by the
+ *   kernel -- the host never waits for it.  An item whose group is outside [0, n_groups) is left untouched.
+ * SGC_EUNSUP for n_groups > SGC_OPTIM_MAX_GROUPS. */
+int sgc_adamw_step_batch(const void *items, int n_items, int total_blocks, const sgc_optim_group *groups, int n_groups,
+                         const float *norm, float max_norm, sgc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

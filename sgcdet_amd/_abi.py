@@ -101,11 +101,23 @@ INTROSPECTION = {
 # include/sgcdet_amd_train.h: training-only entry points (no CPU-oracle twin)
 TRAIN_SIGNATURES = {
     "sgc_plane_sweep_corr_backward": [_p] * 7 + [C.c_int64] + [_i] * 6 + [_p],
+    "sgc_grad_sqnorm_batch": [_p, _i, _i, _p, _p, _p],
+    "sgc_adamw_step_batch": [_p, _i, _i, _p, _i, _p, _f, _p],        # groups: HOST array of sgc_optim_group
 }
 
 TRAIN_INTROSPECTION = {
     "sgc_plane_sweep_corr_backward_workspace_bytes": (C.c_int64, [_i] * 5),
+    "sgc_grad_sqnorm_batch_workspace_bytes": (C.c_int64, [_i]),
 }
+
+
+
+class OptimGroup(C.Structure):
+    """``sgc_optim_group`` of include/sgcdet_amd_train.h: the hyper-parameters of one parameter group, as Python floats."""
+    _fields_ = [("lr", C.c_double), ("weight_decay", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double)]
+
+
+OPTIM_ITEM_BYTES = 64     # sizeof(sgc_optim_item); TensorOps.optim_item_list packs it as "<4Qq4i2f"
 
 ABI_VERSION = 4      # == SGC_ABI_VERSION of include/sgcdet_amd.h (tests/test_abi_cpu.py compares the two)
 

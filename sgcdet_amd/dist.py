@@ -106,10 +106,11 @@ class OverlappedGradAllReduce:
     gradient this step (zeros, as DDP with ``find_unused_parameters=True``), waits, and writes the means back.
 
         sync = OverlappedGradAllReduce(model.parameters())
+        optimizer, scheduler = sgcdet_amd.optim.build_optimizer(model, cfg.optimizer, cfg.lr_scheduler)   # clip 35 + AdamW + OneCycleLR
         for batch in data:
             loss(model, batch).backward()
             sync.finish()
-            optimizer.step(); optimizer.zero_grad(set_to_none=True)
+            optimizer.step(); scheduler.step(); optimizer.zero_grad(set_to_none=True)
     """
 
     def __init__(self, params, bucket_bytes=64 << 20):

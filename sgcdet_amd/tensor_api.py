@@ -859,6 +859,49 @@ class TensorOps:
         if plan is not None:
             self._call("sgc_pack_conv_weight_batch", *plan)
 
+    # ---- the parameter update (include/sgcdet_amd_train.h section 10) ----------
+    OPTIM_BLOCK_ELEMS = 8192         # elements per workgroup of the two optimiser kernels (tools/optim_bench.py sweeps it)
+
+    def optim_item_list(self, entries, block_elems=None):
+        """The ``sgc_optim_item`` list of ``entries`` = [(param, grad, exp_avg, exp_avg_sq, group, step, bias_correction1,
+        bias_correction2_sqrt), ...] as host bytes: ``(blob, n_items, total_blocks)``.  The caller owns the upload (the list changes
+        every step -- ``step`` and, after ``zero_grad(set_to_none=True)``, the gradient addresses); the tensors are the caller's to
+        have checked (``sgcdet_amd.optim`` does: dense fp32 on one device)."""
+        import struct
+        be = int(block_elems or self.OPTIM_BLOCK_ELEMS)
+        if be <= 0 or be % 4:
+            raise ValueError("optim_item_list: block_elems must be a positive multiple of 4")
+        pack, total, parts = struct.Struct("<4Qq4i2f").pack, 0, []
+        for p, g, m, v, group, step, bc1, bc2_sqrt in entries:
+            n = p.numel()
+            if n == 0:
+                continue
+            parts.append(pack(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, group, step, total, be, bc1, bc2_sqrt))
+            total += -(-n // be)
+        if total >= 2 ** 31:
+            raise RuntimeError("optim_item_list: more than 2^31 workgroups")
+        return b"".join(parts), len(parts), total
+
+    def grad_sqnorm_workspace_floats(self, total_blocks):
+        return int(self.lib._dll.sgc_grad_sqnorm_batch_workspace_bytes(int(total_blocks))) // 4
+
+    def grad_sqnorm_batch(self, items, n_items, total_blocks, partials, norm_out):
+        """``norm_out[0]`` = the 2-norm over every gradient of the device item list (``sgc_grad_sqnorm_batch``: two launches, no
+        float atomics -- bitwise reproducible)."""
+        if partials.numel() * 4 < self.lib._dll.sgc_grad_sqnorm_batch_workspace_bytes(int(total_blocks)) or norm_out.numel() < 1:
+            raise RuntimeError("grad_sqnorm_batch: workspace too small")
+        self._call("sgc_grad_sqnorm_batch", items, n_items, total_blocks, partials, norm_out)
+        return norm_out
+
+    def adamw_step_batch(self, items, n_items, total_blocks, groups, norm=None, max_norm=0.0):
+        """One AdamW step of every tensor of the device item list in one launch (``sgc_adamw_step_batch``).  ``groups``:
+        [(lr, weight_decay, beta1, beta2, eps), ...] -- they travel as kernel arguments, not through device memory; ``norm``:
+        1-element device tensor of the gradient norm for clipping at ``max_norm``, or None for no clipping."""
+        from ._abi import OptimGroup
+        arr = (OptimGroup * len(groups))(*[OptimGroup(*(float(x) for x in g)) for g in groups])
+        self._call("sgc_adamw_step_batch", items, n_items, total_blocks, arr, len(groups), norm,
+                   float(max_norm) if norm is not None else 0.0)
+
     def unpack_conv_wgrad(self, dw_trc, shape, transpose=False, flip=False):
         """[T, R, C] fp32 (``conv3d_wgrad_bf16x3``) -> the parameter's layout ``shape`` = [A, B, *taps] (``sgc_unpack_conv_wgrad``)."""
         self._check(dw_trc=dw_trc)

@@ -18,6 +18,9 @@ ap.add_argument("--input-layout", default="nchw", choices=["nchw", "nhwc"],
 ap.add_argument("--wgrad-layers", action="store_true", help="list every weight-gradient call of one step: shapes, kernel form, time")
 ap.add_argument("--cprofile", action="store_true", help="host side: the 45 python functions with the most own time over 5 steps (the step is launch-bound)")
 ap.add_argument("--sites", action="store_true", help="torch ops of one step by the line of this package that issues them (a TorchDispatchMode: forward and backward)")
+ap.add_argument("--optimizer", default="none", choices=["none", "torch", "fused"],
+                help="the parameter update after the backward: none (forward + backward only), torch (clip_grad_norm_(35) + torch.optim.AdamW over "
+                     "the reference's groups, foreach and fused=True both timed, the faster one reported) or fused (sgcdet_amd.optim.FusedAdamW)")
 ap.add_argument("--glue", action="store_true", help="attribute the torch glue ops (copy / add / fill / sum / mul ...) to source lines of this package")
 args = ap.parse_args()
 w = workload(args.workload)
@@ -31,6 +34,8 @@ feats = [f.requires_grad_(True) for f in feats]
 dpt = dpt.requires_grad_(True)
 params = [p for p in det.parameters() if p.requires_grad]
 
+update = [None]      # the parameter update of --optimizer, called after the backward
+
 def step():
     for p in params:
         p.grad = None
@@ -43,23 +48,48 @@ def step():
         r = det.forward_features(feats, [meta], dpt)
         loss = sum((t ** 2).mean() for k in ("centerness", "bbox_pred", "cls_score") for t in r[k]) + r["occ"].mean()
     loss.backward()
+    if update[0] is not None:
+        update[0]()
     return loss.detach()          # no read-back per step: the host issues the next forward while the GPU finishes this backward
 
-for _ in range(2):
-    step()
-# blocks of <= 10 steps, a synchronize between blocks; the reported figure is the MEDIAN block (the host of a shared box stalls for a
-# millisecond now and then and the step is launch-bound in its forward half: a mean over 30 steps moved by +-1 ms between runs)
-blocks = []
-left = args.steps
-while left > 0:
-    n = min(10, left); left -= n
-    torch.cuda.synchronize(); t = time.perf_counter()
-    for _ in range(n):
-        l = step()
-    torch.cuda.synchronize()
-    blocks.append((time.perf_counter() - t) / n * 1e3)
-ms_step = round(sorted(blocks)[len(blocks) // 2], 2)
-ms_min = round(min(blocks), 2)
+def timed_blocks():
+    """blocks of <= 10 steps, a synchronize between blocks; the reported figure is the MEDIAN block (the host of a shared box stalls for a
+    millisecond now and then and the step is launch-bound in its forward half: a mean over 30 steps moved by +-1 ms between runs)"""
+    global l
+    for _ in range(2):
+        step()
+    blocks = []
+    left = args.steps
+    while left > 0:
+        n = min(10, left); left -= n
+        torch.cuda.synchronize(); t = time.perf_counter()
+        for _ in range(n):
+            l = step()
+        torch.cuda.synchronize()
+        blocks.append((time.perf_counter() - t) / n * 1e3)
+    return round(sorted(blocks)[len(blocks) // 2], 2), round(min(blocks), 2)
+
+optimizer_variant, variants_ms = None, {}
+if args.optimizer == "fused":
+    from sgcdet_amd.optim import FusedAdamW, reference_param_groups
+    update[0] = FusedAdamW(reference_param_groups(det, 2e-4, 1e-4), max_grad_norm=35.0).step
+    optimizer_variant = "FusedAdamW"
+    ms_step, ms_min = timed_blocks()
+elif args.optimizer == "torch":
+    from sgcdet_amd.optim import reference_param_groups
+    res = {}
+    for name, kw in (("foreach", dict(foreach=True)), ("fused=True", dict(fused=True))):
+        opt = torch.optim.AdamW(reference_param_groups(det, 2e-4, 1e-4), **kw)
+        update[0] = lambda opt=opt: (torch.nn.utils.clip_grad_norm_(params, 35.0), opt.step())
+        res[name] = timed_blocks()
+        del opt
+    variants_ms = {k: v[0] for k, v in res.items()}
+    optimizer_variant = min(res, key=lambda k: res[k][0])
+    ms_step, ms_min = res[optimizer_variant]
+    update[0] = lambda opt=torch.optim.AdamW(reference_param_groups(det, 2e-4, 1e-4), **(dict(foreach=True) if optimizer_variant == "foreach" else dict(fused=True))): \
+        (torch.nn.utils.clip_grad_norm_(params, 35.0), opt.step())
+else:
+    ms_step, ms_min = timed_blocks()
 l = float(l)
 n_grads = sum(int(p.grad is not None) for p in params)
 if args.profile:
@@ -158,4 +188,5 @@ if args.glue:
         print(f"{t / 1e3:8.3f} ms  x{n:<4d} {name:28s} {site}", file=sys.stderr)
 print(json.dumps(dict(workload=args.workload, ms_per_step=ms_step, ms_per_step_best_block=ms_min, loss=l, params_with_grad=f"{n_grads}/{len(params)}",
                       peak_mem_gb=round(torch.cuda.max_memory_allocated() / 2**30, 2), no_neck=args.no_neck,
-                      input_layout=args.input_layout)))
+                      input_layout=args.input_layout, optimizer=args.optimizer, optimizer_variant=optimizer_variant,
+                      torch_variants_ms=variants_ms)))
