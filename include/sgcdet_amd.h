@@ -56,7 +56,7 @@ extern "C" {
 typedef void *sgc_stream_t; /* hipStream_t */
 
 int sgc_abi_version(void);
-/* Development knobs (A/B of kernel variants and launch geometries in one process; keys in csrc/dfa3d_fwd.hip).  Results do not
+/* Development knobs (A/B of kernel variants and launch geometries in one process; keys in csrc/tuning.hpp).  Results do not
  * depend on them, with one stated exception: "split_target" / "halo_split_target" (and, round 6, "split_free" / "split_min_steps" /
  * "split_max": the tile kernel splits at any K step, see pick_split_steps in csrc/conv3d.hip) choose over how many workgroups a
  * layer with few voxels splits its reduction -- a different split adds the same partial sums in another order (fp32 rounding,

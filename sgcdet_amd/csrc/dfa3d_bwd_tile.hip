@@ -37,6 +37,7 @@
 #include <stdlib.h>
 
 #include "common.hpp"
+#include "tuning.hpp"
 
 namespace sgc {
 
@@ -381,8 +382,6 @@ __global__ __launch_bounds__(NW * 64) void dfa3d_bwd_tile_kernel(const BwdTilePa
     }
   }
 }
-
-int g_tune_bwd_tile_diag = 0;   // timing experiments only (BwdTileParams.diag); inert unless SGC_DIAG=1 is in the environment
 
 }  // namespace sgc
 

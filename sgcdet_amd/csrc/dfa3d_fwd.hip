@@ -21,6 +21,7 @@
 #include <string.h>
 
 #include "common.hpp"
+#include "tuning.hpp"
 
 namespace sgc {
 
@@ -354,34 +355,6 @@ __global__ __launch_bounds__(256) void dfa3d_fwd_wave_kernel(const FwdParams p) 
 //  inputs.  The gather is bound by instruction issue on the load path, not by exposed latency; what did
 //  help is removing the exec-mask branch around every corner load, see Sample::off.)
 
-int g_tune_fwd_variant = 1;
-int g_tune_fwd_spl = 1;         // samples per lane in phase 1 of the wave kernel (1, 2, 4)
-extern int g_tune_conv_waves;   // conv3d.hip: 4 or 8 waves per 128x128 tile
-extern int g_tune_halo_min_cout;
-extern int g_tune_halo_min_m;
-extern int g_tune_halo_brick;
-extern int g_tune_halo_stagger;
-extern int g_tune_halo_small;
-extern int g_tune_wgrad_halo;
-extern int g_tune_view_group;
-extern int g_tune_pq_depth;         // view_pool.hip
-extern int g_tune_halo_wave_fix;     // conv3d.hip
-extern int g_tune_compact2;          // project.hip: two-launch segment form of sgc_compact_pairs
-extern int g_tune_halo_narrow;
-extern int g_tune_split_target, g_tune_split_free, g_tune_split_min_steps, g_tune_split_max;
-extern int g_tune_wgrad_waves;
-extern int g_tune_rows_gemm, g_tune_rows_depth, g_tune_rows_diag, g_tune_igemm_xcd, g_tune_halo_2d, g_tune_rows_cu_pct, g_tune_halo_split_target;
-extern int g_tune_topk_multi_min;
-extern int g_tune_tile_nw;          // dfa3d_tile.hip
-extern int g_tune_tile_depth_lds;
-extern int g_tune_tile_diag;
-extern int g_tune_tile_nbuf;
-extern int g_tune_tile_hg;
-extern int g_tune_tile_ds;
-extern int g_tune_bwd_tile_diag;    // dfa3d_bwd_tile.hip
-extern int g_tune_tile_xcd;
-extern int g_tune_conv_halo;    // conv3d.hip: halo-resident kernel for the 3x3x3 stride-1 layers   // 0: block-barrier kernel, 1: wave-private kernel (when the shape allows)
-
 static int pick_tp(int SPI, int LPI) {
   // enough samples to occupy the block in phase 1, bounded LDS (<= 32 KiB of descriptors)
   int tp = 256 / (SPI > 0 ? SPI : 1);
@@ -541,47 +514,6 @@ extern "C" int sgc_depth_pairs(const float *dist, float *dp, int N, int H, int W
   hipLaunchKernelGGL(depth_pairs_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, dist,
                      reinterpret_cast<float2 *>(dp), total, H, W, D, cam_stride);
   return check_launch("depth_pairs_kernel");
-}
-
-extern "C" int sgc_set_tuning(const char *key, int value) {
-  if (!key) return set_error(SGC_EINVAL, "sgc_set_tuning: null key");
-  if (!strcmp(key, "fwd_variant")) { g_tune_fwd_variant = value; return SGC_OK; }
-  if (!strcmp(key, "conv_waves")) { g_tune_conv_waves = value; return SGC_OK; }
-  if (!strcmp(key, "fwd_spl")) { g_tune_fwd_spl = value; return SGC_OK; }
-  if (!strcmp(key, "conv_halo")) { g_tune_conv_halo = value; return SGC_OK; }
-  if (!strcmp(key, "halo_min_cout")) { g_tune_halo_min_cout = value; return SGC_OK; }
-  if (!strcmp(key, "halo_min_m")) { g_tune_halo_min_m = value; return SGC_OK; }
-  if (!strcmp(key, "halo_brick")) { g_tune_halo_brick = value; return SGC_OK; }
-  if (!strcmp(key, "halo_stagger")) { g_tune_halo_stagger = value; return SGC_OK; }
-  if (!strcmp(key, "halo_small")) { g_tune_halo_small = value; return SGC_OK; }
-  if (!strcmp(key, "wgrad_halo")) { g_tune_wgrad_halo = value; return SGC_OK; }
-  if (!strcmp(key, "view_group")) { g_tune_view_group = value; return SGC_OK; }
-  if (!strcmp(key, "view_depth")) { g_tune_pq_depth = value; return SGC_OK; }
-  if (!strcmp(key, "compact2")) { g_tune_compact2 = value; return SGC_OK; }
-  if (!strcmp(key, "halo_wave_fix")) { g_tune_halo_wave_fix = value; return SGC_OK; }
-  if (!strcmp(key, "halo_narrow")) { g_tune_halo_narrow = value; return SGC_OK; }
-  if (!strcmp(key, "split_target")) { g_tune_split_target = value; return SGC_OK; }
-  if (!strcmp(key, "split_free")) { g_tune_split_free = value; return SGC_OK; }
-  if (!strcmp(key, "split_min_steps")) { g_tune_split_min_steps = value > 0 ? value : 1; return SGC_OK; }
-  if (!strcmp(key, "split_max")) { g_tune_split_max = value > 0 ? value : 1; return SGC_OK; }
-  if (!strcmp(key, "wgrad_waves")) { g_tune_wgrad_waves = value; return SGC_OK; }
-  if (!strcmp(key, "rows_gemm")) { g_tune_rows_gemm = value; return SGC_OK; }
-  if (!strcmp(key, "igemm_xcd")) { g_tune_igemm_xcd = value; return SGC_OK; }
-  if (!strcmp(key, "halo_2d")) { g_tune_halo_2d = value; return SGC_OK; }
-  if (!strcmp(key, "rows_cu_pct")) { g_tune_rows_cu_pct = value; return SGC_OK; }
-  if (!strcmp(key, "halo_split_target")) { g_tune_halo_split_target = value; return SGC_OK; }
-  if (!strcmp(key, "rows_depth")) { g_tune_rows_depth = value; return SGC_OK; }
-  if (!strcmp(key, "rows_diag")) { g_tune_rows_diag = value; return SGC_OK; }      // inert without SGC_DIAG=1 (rows_gemm.hip)
-  if (!strcmp(key, "topk_multi_min")) { g_tune_topk_multi_min = value; return SGC_OK; }
-  if (!strcmp(key, "tile_nw")) { g_tune_tile_nw = value; return SGC_OK; }
-  if (!strcmp(key, "tile_depth_lds")) { g_tune_tile_depth_lds = value; return SGC_OK; }
-  if (!strcmp(key, "tile_diag")) { g_tune_tile_diag = value; return SGC_OK; }
-  if (!strcmp(key, "tile_nbuf")) { g_tune_tile_nbuf = value; return SGC_OK; }
-  if (!strcmp(key, "tile_hg")) { g_tune_tile_hg = value; return SGC_OK; }
-  if (!strcmp(key, "tile_ds")) { g_tune_tile_ds = value; return SGC_OK; }
-  if (!strcmp(key, "bwd_tile_diag")) { g_tune_bwd_tile_diag = value; return SGC_OK; }
-  if (!strcmp(key, "tile_xcd")) { g_tune_tile_xcd = value; return SGC_OK; }
-  return set_error(SGC_EINVAL, "sgc_set_tuning: unknown key %s", key);
 }
 
 extern "C" int sgc_dfa3d_forward(const float *value, const float *dist, const int64_t *shapes3,

@@ -30,6 +30,7 @@
 #include <stdlib.h>
 
 #include "common.hpp"
+#include "tuning.hpp"
 
 namespace sgc {
 
@@ -527,27 +528,25 @@ __global__ __launch_bounds__(NW * 64) void dfa3d_fwd_tile_kernel(const TileParam
   if (p.diag == 1 && tid == 0) p.out[(int64_t)i0 * p.M * CM] = (float)val0[0] + (DL ? dep[0] : 0.f);
 }
 
-// A/B knobs (sgc_set_tuning); 0 = the library's own choice.  Results never depend on them.
-int g_tune_tile_nw = 0;         // waves per workgroup (8 or 16).  auto: 8 when two workgroups fit a CU's LDS (<= 80 KB
-                                // each: one computes while the other stages its window), else 16
-int g_tune_tile_depth_lds = -1; // >= 0 overrides the caller's depth_in_lds
-int g_tune_tile_diag = 0;       // TIMING EXPERIMENTS ONLY (1 = no compute, 2 = no fill: the outputs are garbage); inert unless
-                                // SGC_DIAG=1 is in the environment, so a stray SGC_TUNE cannot corrupt a production run
+// A/B knobs (tuning.hpp: tile_*); 0 = the library's own choice.  Results never depend on them.
+// tile_nw       waves per workgroup (8 or 16).  auto: 8 when two workgroups fit a CU's LDS (<= 80 KB
+//               each: one computes while the other stages its window), else 16
+// tile_diag     TIMING EXPERIMENTS ONLY (1 = no compute, 2 = no fill: the outputs are garbage); inert unless
+//               SGC_DIAG=1 is in the environment, so a stray SGC_TUNE cannot corrupt a production run
 static bool diag_allowed() {
   static const bool ok = getenv("SGC_DIAG") && atoi(getenv("SGC_DIAG")) == 1;
   return ok;
 }
-int g_tune_tile_nbuf = 0;       // value-window buffers; 2 = the next head's window lands while the current head is computed
-                                // (needs heads-per-workgroup > 1).  auto: 1
-int g_tune_tile_xcd = -1;       // 1: camera n's workgroups on XCD n % 8 (head-major, bins innermost); 0: (camera, bin, head) order,
-                                // i.e. head h on XCD h; -1 (default): 1 at Cm = 32, 0 at Cm = 16.  Same time at config 2 (round 3,
-                                // alternated bench runs: 95.8 / 97.5 vs 96.6 / 96.4 us) but a third less traffic on the memory side
-                                // of the L2s: rocprofv3 --pmc FETCH_SIZE (doubled) + WRITE_SIZE = 435 MB -> 335 MB per launch = 1.30 ->
-                                // 1.00 x the algorithmic bytes (profiles/r03_gather_tile_pmc_hbm.json) -- with head h on XCD h every
-                                // camera's depth map was fetched through all eight L2s.  Config 4 (Cm = 16, depth window in LDS) was
-                                // 8 % slower with 1 (round 2: 385 vs 420 us) and keeps 0.
-int g_tune_tile_hg = 0;         // heads per workgroup.  auto: 1 (most workgroups: (camera, bin, head))
-int g_tune_tile_ds = 1;         // 1: one window test for value and depth where the two windows coincide (template flag DS); 0: A/B
+// tile_nbuf     value-window buffers; 2 = the next head's window lands while the current head is computed
+//               (needs heads-per-workgroup > 1).  auto: 1
+// tile_xcd      1: camera n's workgroups on XCD n % 8 (head-major, bins innermost); 0: (camera, bin, head) order,
+//               i.e. head h on XCD h; -1 (default): 1 at Cm = 32, 0 at Cm = 16.  Same time at config 2 (round 3,
+//               alternated bench runs: 95.8 / 97.5 vs 96.6 / 96.4 us) but a third less traffic on the memory side
+//               of the L2s: rocprofv3 --pmc FETCH_SIZE (doubled) + WRITE_SIZE = 435 MB -> 335 MB per launch = 1.30 ->
+//               1.00 x the algorithmic bytes (profiles/r03_gather_tile_pmc_hbm.json) -- with head h on XCD h every
+//               camera's depth map was fetched through all eight L2s.  Config 4 (Cm = 16, depth window in LDS) was
+//               8 % slower with 1 (round 2: 385 vs 420 us) and keeps 0.
+// tile_hg       heads per workgroup.  auto: 1 (most workgroups: (camera, bin, head))
 
 }  // namespace sgc
 

@@ -22,9 +22,6 @@
 
 namespace sgc {
 
-int g_tune_level_tail = 1;       // 0: the six separate launches (round-2 path)
-
-
 struct LevelTailParams {
   const float *ctx;              // [rows, C] compact rows of the voxels some camera sees (view_attend's output)
   const int32_t *row_of;         // [Nq]: compact row of voxel q, -1 = seen by no camera
@@ -273,7 +270,7 @@ static int launch_level_tail(const LevelTailParams &p, hipStream_t st) {
 
 using namespace sgc;
 
-extern "C" int sgc_level_tail_supported(int C, int F) { return g_tune_level_tail && (C == 128 || C == 256) && F == 2 * C; }
+extern "C" int sgc_level_tail_supported(int C, int F) { return (C == 128 || C == 256) && F == 2 * C; }
 
 extern "C" int sgc_level_tail(const float *ctx, const int32_t *row_of, const uint16_t *wo_hi, const uint16_t *wo_lo, const float *bo,
                               const float *ln1_gamma, const float *ln1_beta, float eps1, const uint16_t *w1_hi,

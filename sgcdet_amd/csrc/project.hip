@@ -5,6 +5,7 @@
 // of DeformCrossAttention_DFA3D.forward (TU/deformable_cross_attention.py:759-773, N host
 // syncs per level) by four tiny launches and ONE optional host read (the 4 ints of `totals`).
 #include "common.hpp"
+#include "tuning.hpp"
 
 namespace sgc {
 
@@ -248,8 +249,6 @@ __global__ __launch_bounds__(1024) void pairs_scan2_kernel(int N, int Nq, int S,
     }
   }
 }
-
-int g_tune_compact2 = 1;       // 1: the two-launch segment form of sgc_compact_pairs (needs the workspace), 0: the five kernels
 
 }  // namespace sgc
 

@@ -14,6 +14,7 @@
 //                     build_norm_layer(dict(type='LN')), TU/custom_base_transformer_layer.py:153-156): one wave per
 //                     row, two-pass mean / biased variance in registers, rsqrt(var + eps), affine.
 #include "common.hpp"
+#include "tuning.hpp"
 
 namespace sgc {
 
@@ -371,10 +372,9 @@ __global__ __launch_bounds__(256) void layer_norm_rows_generic_kernel(const floa
 
 using namespace sgc;
 
-// candidate sets of at least this size use the many-workgroup form (7 launches) when a workspace is given.  Round 5: 32 769 -- up to 32 768
+// topk_multi_min: candidate sets of at least this size use the many-workgroup form (7 launches) when a workspace is given.  Round 5: 32 769 -- up to 32 768
 // candidates ONE workgroup with the keys in registers is as fast with one or four scenes in flight (573 / 566 / 579 against 574 / 567 / 564
 // scenes/s, 388 against 389 with one stream: profiles/r05_topk_ab.txt) and is one launch; it was 16 384 since round 3
-namespace sgc { int g_tune_topk_multi_min = 32769; }
 
 extern "C" int64_t sgc_topk_select_workspace_bytes(int n) {
   return n > 0 ? (int64_t)(4 * 256 + 2 * ceil_div(n, TK_CHUNK)) * (int64_t)sizeof(int) : 0;

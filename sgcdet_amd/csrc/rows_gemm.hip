@@ -30,22 +30,22 @@
 #include <stdlib.h>
 
 #include "common.hpp"
+#include "tuning.hpp"
 #include "mma.hpp"
 #include "diag.hpp"
 
 namespace sgc {
 
-int g_tune_rows_gemm = 1;        // 0: every row GEMM on the tile-per-workgroup implicit-GEMM kernel (round-2 path)
-int g_tune_rows_diag = 0;        // TIMING EXPERIMENTS ONLY, honoured only with SGC_DIAG=1 in the environment (results are then
-                                 // invalid): bit 0 = stores dropped by the range check, bit 1 = loads dropped (zeros), bit 2 = no MFMA
-int g_tune_rows_cu_pct = 100;   // persistent row GEMM: share of the CUs it occupies (it is memory-bound: with scenes in flight the rest serve MFMA kernels)
-int g_tune_rows_depth = 1;       // 8-wave form: 1 / 2 = lockstep with that many tiles in flight ahead of the one being multiplied,
-                                 // 0 = staggered halves (waves 4-7 half a period behind waves 0-3); the 4-wave form (two workgroups
-                                 // per CU) is lockstep, 1 ahead.  Interleaved A/B on the 204,800 x 256 -> 256 Linear (3 rounds x 40
-                                 // launches): lockstep-1 90-93 us row-major / 94-98 head-major, lockstep-2 92-93 / 98-101, staggered
-                                 // 96-100 / 97-104 (in-kernel stamps: a staging phase issues ~350 instructions per wave and tile and
-                                 // slows the partner wave's MFMA chain from 1536 to 2000-3000 cycles, so separating the phases in
-                                 // time does not pay); the memory-only form of the kernel (no MFMA) takes 80 us = 5.2 TB/s
+// rows_diag    TIMING EXPERIMENTS ONLY, honoured only with SGC_DIAG=1 in the environment (results are then
+//              invalid): bit 0 = stores dropped by the range check, bit 1 = loads dropped (zeros), bit 2 = no MFMA
+// rows_cu_pct  the kernel is memory-bound: with scenes in flight the CUs it leaves serve MFMA kernels
+// rows_depth   8-wave form: 1 / 2 = lockstep with that many tiles in flight ahead of the one being multiplied,
+//              0 = staggered halves (waves 4-7 half a period behind waves 0-3); the 4-wave form (two workgroups
+//              per CU) is lockstep, 1 ahead.  Interleaved A/B on the 204,800 x 256 -> 256 Linear (3 rounds x 40
+//              launches): lockstep-1 90-93 us row-major / 94-98 head-major, lockstep-2 92-93 / 98-101, staggered
+//              96-100 / 97-104 (in-kernel stamps: a staging phase issues ~350 instructions per wave and tile and
+//              slows the partner wave's MFMA chain from 1536 to 2000-3000 cycles, so separating the phases in
+//              time does not pay); the memory-only form of the kernel (no MFMA) takes 80 us = 5.2 TB/s
 
 
 struct RowsGemmParams {

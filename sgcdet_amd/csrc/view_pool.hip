@@ -5,12 +5,12 @@
 // with -inf (TU/deformable_cross_attention.py:815-833).  Here the visible (camera, query)
 // pairs stay a compact list; `slot[n,q]` (pair index or -1) is the only dense object.
 #include "common.hpp"
+#include "tuning.hpp"
 
 namespace sgc {
 
-int g_tune_pq_depth = 4;      // knob view_depth: pair rows in flight per lane in view_attend_pq_kernel (1 | 2 | 4 | 8) and in the
-                               // group kernels of view_mean / view_attend (>= 4: four, else one) -- A/B; results identical
-int g_tune_view_group = 1;     // 0: the per-camera loops of rounds 1-2 in view_mean / view_attend (A/B; results identical)
+// g_tune_pq_depth (key view_depth): pair rows in flight per lane in view_attend_pq_kernel (1 | 2 | 4 | 8) and in the
+// group kernels of view_mean / view_attend (>= 4: four, else one) -- A/B; results identical
 
 // mean over the cameras that see voxel valid_index[i]; C/4 lanes per voxel (float4 rows)
 // LG = C/4 in {32, 64}: the lanes of a voxel form a GROUP inside one wave.  Round 3: the group reads the voxel's slot column

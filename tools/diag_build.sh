@@ -8,7 +8,7 @@ mkdir -p tools/diag/obj_$name
 objs=""
 for f in sgcdet_amd/csrc/*.hip; do
   o=sgcdet_amd/csrc/$(basename ${f%.hip}).o
-  if [ "$(basename $f)" == "$src" ]; then
+  if [[ "$(basename $f)" == $src ]]; then    # <file.hip> may be a pattern: 'conv3d_halo*.hip'
     o=tools/diag/obj_$name/$(basename ${f%.hip}).o
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c $f -o $o -Xclang -target-feature -Xclang -packed-fp32-ops "$@"
   fi

@@ -1,6 +1,6 @@
 """Where the halo convolution's tap loop spends its time (the 90-GF layer 256 -> 256 at 40x40x16; SGC_HALO_STAGGER=0: the lockstep form): the product
 library against timing builds with parts of the loop removed (SGC_HALO_SKIP, csrc/diag.hpp; their results are garbage):
-  for m in 1 2 4 8 16 6 24 31; do bash tools/diag_build.sh skip$m conv3d.hip -DSGC_HALO_SKIP=$m; done
+  for m in 1 2 4 8 16 6 24 31; do bash tools/diag_build.sh skip$m 'conv3d_halo*.hip' -DSGC_HALO_SKIP=$m; done
 Alternated rounds in one process; the first round is the cold one."""
 import glob, os, re, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -1,6 +1,6 @@
 """Where the tile implicit GEMM (conv3d_igemm_bf16x3_kernel) spends its time on the layers the halo kernel cannot take -- the product
 library against timing builds with parts of the K loop removed (SGC_TILE_SKIP, csrc/diag.hpp; THEIR RESULTS ARE GARBAGE):
-  for m in 1 2 4 8 14 16 32 64; do bash tools/diag_build.sh tskip$m conv3d.hip -DSGC_TILE_SKIP=$m; done
+  for m in 1 2 4 8 14 16 32 64; do bash tools/diag_build.sh tskip$m conv3d_igemm.hip -DSGC_TILE_SKIP=$m; done
 bits: 1 no MFMAs, 2 no input loads, 4 no weight loads, 8 no split + LDS stores, 16 no fragment reads, 32 no barrier per step,
 64 no epilogue.  Alternated rounds in one process (the first one is cold), median of the rest."""
 import glob, os, re, sys, torch
