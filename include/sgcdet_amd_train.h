@@ -94,6 +94,68 @@ int64_t sgc_grad_sqnorm_batch_workspace_bytes(int total_blocks);
 int sgc_adamw_step_batch(const void *items, int n_items, int total_blocks, const sgc_optim_group *groups, int n_groups,
                          const float *norm, float max_norm, sgc_stream_t stream);
 
+/* ------------------------------------------------------------------------- *
+ * 11. The loss of the detection head with its gradients (csrc/head_loss.hip)
+ * ------------------------------------------------------------------------- */
+
+/* The head tensors of one scale, for one image, read where the head produced them: element (channel c, point j) of a tensor is at
+ * base[c * channel_stride + j * point_stride] (strides in elements, positive), j = (x * Y + y) * Z + z -- the order of get_points and
+ * of the flattened point list.  [C, X, Y, Z] contiguous is (X*Y*Z, 1); the channels-last rows of the convolutions are (1, row length).
+ *   centerness 1 channel (logit);  bbox_pred n_reg channels, already activated (6 face distances [+ the raw angle]);
+ *   cls_score n_classes channels (logits);  valid [n_points] bytes, non-zero = inside some camera's view. */
+typedef struct sgc_head_loss_level {
+  const float *centerness, *bbox_pred, *cls_score;
+  const uint8_t *valid;
+  int64_t n_points;                                  /* X * Y * Z */
+  int32_t centerness_point_stride, bbox_channel_stride, bbox_point_stride, cls_channel_stride, cls_point_stride, reserved;
+} sgc_head_loss_level;            /* 64 bytes */
+#define SGC_HEAD_LOSS_MAX_SCALES 4
+
+/* ImVoxelHeadV2._loss_single (imvoxel_head_v2.py:147-235) for one image: pos = labels >= 0 & valid, n = max(count(pos), 1),
+ *   losses[0] = lw_centerness * sum_pos BCEWithLogits(centerness, centerness_targets) / n
+ *   losses[1] = lw_bbox * sum_pos w (1 - IoU(decode(point, bbox_pred), bbox_targets)) / sum_pos w,   w = centerness_targets
+ *   losses[2] = lw_cls * sum_valid sum_c sigmoid_focal(cls_score, labels; gamma, alpha) / n
+ * with log(max(p, FLT_MIN)) in the focal loss (zero gradient where the clamp is active), any label outside [0, n_classes) background
+ * for every class; rotated = 0: n_reg = 6, boxes (x0,y0,z0,x1,y1,z1) = point -/+ distances, axis-aligned IoU with eps = 1e-6;
+ * rotated = 1: n_reg = 7, boxes (cx,cy,cz,w,l,h,angle) with the centre shift rotated by the predicted angle, IoU of rotated boxes
+ * (rectangle clipped against the four edges of the target, shoelace area, z overlap, inter / (vol - inter)).  Empty cases are decided
+ * on the device: no valid point -> losses[2] = 0; no positive or sum w = 0 -> losses[0] = losses[1] = 0 (sum w = 0 alone: only
+ * losses[1]); the corresponding gradients are 0.
+ *   levels: n_scales <= SGC_HEAD_LOSS_MAX_SCALES structs in HOST memory, copied into the kernels' arguments;
+ *   points [n_points, 3], centerness_targets [n_points], bbox_targets [n_points, n_reg], labels [n_points] int64: the flattened
+ *   point list (level after level) and the outputs of sgc_assign_targets for it; targets of non-positive points are never read;
+ *   gamma, alpha, lw_*: as torch holds them (Python floats);
+ *   n_pos_override: NULL, or 1 float in DEVICE memory that replaces count(pos) in n (a distributed run's all-reduced mean);
+ *   losses [3], n_pos [1] (the LOCAL count, whatever n_pos_override says): device floats, written;
+ *   grads: the packed gradient buffer, (1 + n_reg + n_classes) * n_points floats, EVERY element written (nothing to pre-zero):
+ *     level l starts at (1 + n_reg + n_classes) * (points of the levels before it) and holds the planes [1 + n_reg + n_classes,
+ *     n_points_l] contiguous -- centerness, bbox_pred, cls_score, each a [C, X, Y, Z] contiguous tensor.  It holds the UNNORMALISED
+ *     gradients; sgc_head_loss_scale_grads turns them into d (sum_k grad_k * losses[k]) / d tensor;
+ *   workspace >= sgc_head_loss_workspace_bytes(n_points, n_scales) bytes, 8-byte aligned, contents irrelevant before; afterwards it
+ *     holds the per-workgroup partial sums and the three scale factors that sgc_head_loss_finalize / sgc_head_loss_scale_grads read.
+ * Two launches (three with rotated = 1), no host read-back, no float atomics: bitwise reproducible run to run.
+ * SGC_EUNSUP for n_scales > SGC_HEAD_LOSS_MAX_SCALES, n_reg not 6 / 7, rotated not matching n_reg, levels whose n_points do not add
+ * up to n_points, n_points * (1 + n_reg + n_classes) >= 2^31. */
+int sgc_head_loss_forward(const sgc_head_loss_level *levels, int n_scales, const float *points, const float *centerness_targets,
+                          const float *bbox_targets, const int64_t *labels, int n_points, int n_reg, int n_classes, int rotated,
+                          double gamma, double alpha, double lw_centerness, double lw_bbox, double lw_cls, const float *n_pos_override,
+                          float *losses, float *n_pos, float *grads, void *workspace, int64_t workspace_bytes, sgc_stream_t stream);
+int64_t sgc_head_loss_workspace_bytes(int n_points, int n_scales);
+
+/* The last launch of sgc_head_loss_forward again, on the workspace it left: losses, n_pos and the scale factors for another
+ * n_pos_override.  A distributed run calls the forward without an override, all-reduces n_pos on the device and calls this.
+ *   level_points: n_scales int64 in HOST memory, the n_points of the levels. */
+int sgc_head_loss_finalize(void *workspace, int64_t workspace_bytes, const int64_t *level_points, int n_scales,
+                           const float *n_pos_override, double lw_centerness, double lw_bbox, double lw_cls, float *losses, float *n_pos,
+                           sgc_stream_t stream);
+
+/* out = grads * (scale factor of the element's loss) * (upstream gradient of that loss), one launch over the packed gradient buffer;
+ * out may be grads itself.  grad_centerness / grad_bbox / grad_cls: 1 float each in DEVICE memory (autograd's grad_outputs);
+ * workspace: the one sgc_head_loss_forward (or _finalize) wrote last;  level_points as above. */
+int sgc_head_loss_scale_grads(const float *grads, float *out, const int64_t *level_points, int n_scales, int n_reg, int n_classes,
+                              const void *workspace, const float *grad_centerness, const float *grad_bbox, const float *grad_cls,
+                              sgc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

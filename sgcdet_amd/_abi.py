@@ -13,6 +13,7 @@ import ctypes as C
 _p = C.c_void_p
 _i = C.c_int
 _f = C.c_float
+_d = C.c_double
 
 # name -> argtypes (restype is int for all but the introspection / query calls)
 SIGNATURES = {
@@ -103,13 +104,16 @@ TRAIN_SIGNATURES = {
     "sgc_plane_sweep_corr_backward": [_p] * 7 + [C.c_int64] + [_i] * 6 + [_p],
     "sgc_grad_sqnorm_batch": [_p, _i, _i, _p, _p, _p],
     "sgc_adamw_step_batch": [_p, _i, _i, _p, _i, _p, _f, _p],        # groups: HOST array of sgc_optim_group
+    "sgc_head_loss_forward": [_p, _i] + [_p] * 4 + [_i] * 4 + [_d] * 5 + [_p] * 5 + [C.c_int64, _p],      # levels: HOST array of sgc_head_loss_level
+    "sgc_head_loss_finalize": [_p, C.c_int64, _p, _i, _p] + [_d] * 3 + [_p] * 3,                         # level_points: HOST int64 array
+    "sgc_head_loss_scale_grads": [_p, _p, _p] + [_i] * 3 + [_p] * 5,
 }
 
 TRAIN_INTROSPECTION = {
     "sgc_plane_sweep_corr_backward_workspace_bytes": (C.c_int64, [_i] * 5),
     "sgc_grad_sqnorm_batch_workspace_bytes": (C.c_int64, [_i]),
+    "sgc_head_loss_workspace_bytes": (C.c_int64, [_i] * 2),
 }
-
 
 
 class OptimGroup(C.Structure):
@@ -118,6 +122,8 @@ class OptimGroup(C.Structure):
 
 
 OPTIM_ITEM_BYTES = 64     # sizeof(sgc_optim_item); TensorOps.optim_item_list packs it as "<4Qq4i2f"
+HEAD_LOSS_LEVEL_BYTES = 64     # sizeof(sgc_head_loss_level); TensorOps.head_loss packs it as "<4Qq6i"
+HEAD_LOSS_MAX_SCALES = 4       # SGC_HEAD_LOSS_MAX_SCALES
 
 ABI_VERSION = 4      # == SGC_ABI_VERSION of include/sgcdet_amd.h (tests/test_abi_cpu.py compares the two)
 

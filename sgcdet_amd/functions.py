@@ -316,6 +316,47 @@ class PlaneSweepCorrFunction(Function):
         return grad_rows, None, None, None, None, None
 
 
+class HeadLossFunction(Function):
+    """``ImVoxelHeadV2._loss_single`` (imvoxel_head_v2.py:147-235) for one image on the HIP kernels of csrc/head_loss.hip:
+    forward ``sgc_head_loss_forward`` (values and unnormalised gradients in one pass), backward ``sgc_head_loss_scale_grads`` -- at most
+    four launches for both passes, no host synchronisation.
+
+    ``apply(points, centerness_targets, bbox_targets, labels, n_pos_override, cfg, *head)`` -> (loss_centerness, loss_bbox, loss_cls),
+    three scalars.  ``head``: the 4 * n_scales tensors centerness[0..], bbox_pred[0..], cls_score[0..], valid[0..] (bbox_pred after its
+    activation, [C,X,Y,Z] each, valid bool / uint8).  ``cfg`` = dict(rotated, gamma, alpha, loss_weights=(centerness, bbox, cls),
+    reduce_n_pos): with ``reduce_n_pos`` and an initialised process group the local count of positives is all-reduced (mean) as a
+    device tensor and the losses are normalised by it, as mmdet's ``reduce_mean`` does.  ``n_pos_override``: None or a 1-element device
+    tensor that replaces the count.  Only the centerness / bbox_pred / cls_score tensors are differentiable; points, targets, labels
+    and valid get no gradient."""
+
+    @staticmethod
+    def forward(ctx, points, centerness_targets, bbox_targets, labels, n_pos_override, cfg, *head):
+        if len(head) % 4 or not head:
+            raise RuntimeError("HeadLossFunction: centerness, bbox_pred, cls_score and valid tensors of every scale expected")
+        L = len(head) // 4
+        for t in head[:3 * L]:
+            if t.dtype != torch.float32:      # the kernels read fp32; a silent .float() would hide an autocast region around the loss
+                raise TypeError(f"HeadLossFunction: the head tensors must be float32 (got {t.dtype}); run the loss outside autocast")
+        ops = ext.ops()
+        det = [t.detach() for t in head]
+        losses, n_pos, state = ops.head_loss(det[:L], det[L:2 * L], det[2 * L:3 * L], [v.reshape(-1) for v in det[3 * L:]], points,
+                                             centerness_targets, bbox_targets, labels, cfg["rotated"], cfg.get("gamma", 2.0),
+                                             cfg.get("alpha", 0.25), cfg.get("loss_weights", (1.0, 1.0, 1.0)), n_pos_override)
+        if n_pos_override is None and cfg.get("reduce_n_pos") and torch.distributed.is_available() and torch.distributed.is_initialized():
+            torch.distributed.all_reduce(n_pos.div_(torch.distributed.get_world_size()))          # mmdet reduce_mean, on the device
+            losses, _ = ops.head_loss_finalize(state, n_pos)
+        ctx.state, ctx.n_scales = state, L
+        return losses[0], losses[1], losses[2]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_centerness, grad_bbox, grad_cls):
+        L = ctx.n_scales
+        ctr, reg, cls = ext.ops().head_loss_grads(ctx.state, grad_centerness.float().contiguous(), grad_bbox.float().contiguous(),
+                                                  grad_cls.float().contiguous())
+        return (None,) * 6 + tuple(ctr) + tuple(reg) + tuple(cls) + (None,) * L
+
+
 def _pad_cols(t, mult):
     """[rows, C] -> [rows, ceil(C / mult) * mult] with zero columns (a view when nothing is added)."""
     c = t.shape[-1]

@@ -14,13 +14,15 @@ NMS (row f-4): ScanNet's ``aligned_3d_nms`` (mmdet3d, a Python while-loop in the
 rotated-rectangle intersection in the reference kernel's fp32 operation order, pinned to the copy of mmcv's
 ``box_iou_rotated_utils.hpp`` the reference carries in its DFA3D package -- tests/golden/box_iou_rotated.npz).
 """
+import os
+
 import torch
 from torch import nn
 
 from .. import ext
 from ..mmcv_lite import HEADS, LOSSES, Scale, bias_init_with_prob, multi_apply, normal_init
 from .conv_plan import train_conv_on_hip, ConvSpec, module_fingerprint, rows_to_ncdhw, to_channels_last_rows
-from . import losses  # noqa: F401  (registers the LOSSES entries the head builds)
+from . import losses  # registers the LOSSES entries the head builds
 
 
 @torch.no_grad()
@@ -220,12 +222,39 @@ class ImVoxelHeadV2(nn.Module):
         return ext.ops().assign_targets(pts, scales, self._gt_rows(gt_bboxes, dev), gt_labels.to(torch.int64).contiguous(),
                                         self.rotated_targets, self.n_scales, self.limit, self.centerness_topk)
 
+    fused_loss_bbox = None           # the registered IoU loss whose arithmetic the fused operator restates for this head class
+
+    def _fused_loss(self, tensors):
+        """The fused loss (``functions.HeadLossFunction``, csrc/head_loss.hip) restates exactly the registered FocalLoss /
+        CrossEntropyLoss / AxisAlignedIoULoss | RotatedIoU3DLoss under ``reduction='mean'`` with this head class's box decoding on
+        fp32 GPU tensors; anything else -- CPU tensors, a user-supplied loss module or decoding, another reduction, another dtype,
+        more scales than the kernel takes -- keeps the torch path below.  ``SGC_HEAD_LOSS_FUSED=0`` forces the torch path (A/B runs)."""
+        if os.environ.get("SGC_HEAD_LOSS_FUSED", "1") == "0" or self.fused_loss_bbox is None:
+            return False
+        if not all(t.is_cuda and t.dtype == torch.float32 for t in tensors) or len(tensors) > 3 * 4:
+            return False
+        mods = ((self.loss_cls, losses.FocalLoss), (self.loss_centerness, losses.CrossEntropyLoss), (self.loss_bbox, self.fused_loss_bbox))
+        if not all(type(m) is cls and m.reduction == "mean" for m, cls in mods):
+            return False
+        base = ScanNetImVoxelHeadV2 if self.fused_loss_bbox is losses.AxisAlignedIoULoss else SunRgbdImVoxelHeadV2
+        return isinstance(self, base) and type(self)._bbox_pred_to_bbox is base._bbox_pred_to_bbox
+
     def _loss_single(self, centernesses, bbox_preds, cls_scores, valids, img_meta, gt_bboxes, gt_labels):
         """(:147-235)."""
         dev = centernesses[0].device
         sizes = [f.size()[-3:] for f in centernesses]
         mlvl_points = self.get_points(sizes, img_meta["lidar2img"]["origin"], dev)
         ctr_t, box_t, labels, geo_occ = self.get_targets(mlvl_points, gt_bboxes, gt_labels.to(dev))
+        if self._fused_loss(centernesses + bbox_preds + cls_scores):
+            # one fused operator on the head tensors where they lie: values and gradients in <= 4 launches, no host synchronisation
+            from ..functions import HeadLossFunction
+            cfg = dict(rotated=self.rotated_targets, gamma=self.loss_cls.fn_kwargs["gamma"], alpha=self.loss_cls.fn_kwargs["alpha"],
+                       loss_weights=(self.loss_centerness.loss_weight, self.loss_bbox.loss_weight, self.loss_cls.loss_weight),
+                       reduce_n_pos=True)
+            points = torch.cat(mlvl_points).to(dtype=torch.float32).contiguous()
+            loss_centerness, loss_bbox, loss_cls = HeadLossFunction.apply(points, ctr_t, box_t, labels, None, cfg, *centernesses,
+                                                                          *bbox_preds, *cls_scores, *valids)
+            return loss_centerness, loss_bbox, loss_cls, labels, geo_occ
         n_reg = bbox_preds[0].shape[0]
         ctr = torch.cat([c.permute(1, 2, 3, 0).reshape(-1) for c in centernesses])
         reg = torch.cat([r.permute(1, 2, 3, 0).reshape(-1, n_reg) for r in bbox_preds])
@@ -265,6 +294,7 @@ class ImVoxelHeadV2(nn.Module):
 @HEADS.register_module()
 class ScanNetImVoxelHeadV2(ImVoxelHeadV2):
     default_loss_bbox = "AxisAlignedIoULoss"      # configs/SGCDet_ScanNet.py:111
+    fused_loss_bbox = losses.AxisAlignedIoULoss
 
     def forward_single(self, x, scale):
         return self.centerness_conv(x), torch.exp(scale(self.reg_conv(x))), self.cls_conv(x)
@@ -301,6 +331,7 @@ class ScanNetImVoxelHeadV2(ImVoxelHeadV2):
 class SunRgbdImVoxelHeadV2(ImVoxelHeadV2):
     rotated_targets = True
     default_loss_bbox = "RotatedIoU3DLoss"        # configs/SGCDet_ARKit.py:114
+    fused_loss_bbox = losses.RotatedIoU3DLoss
 
     def forward_single(self, x, scale):
         reg = self.reg_conv(x)

@@ -902,6 +902,120 @@ class TensorOps:
         self._call("sgc_adamw_step_batch", items, n_items, total_blocks, arr, len(groups), norm,
                    float(max_norm) if norm is not None else 0.0)
 
+    # ---- the loss of the detection head (include/sgcdet_amd_train.h section 11) ----------
+    @staticmethod
+    def _point_strides(t):
+        """(channel stride, point stride) of a [C, X, Y, Z] tensor whose points j = (x * Y + y) * Z + z lie at a constant stride
+        (contiguous, or the channels-last views of the convolution rows), else None."""
+        (_, X, Y, Z), (sc, sx, sy, sz) = t.shape, t.stride()
+        ps = sz if Z > 1 else (sy if Y > 1 else sx)
+        if (Z > 1 and Y > 1 and sy != Z * sz) or (Y * Z > 1 and X > 1 and sx != Y * Z * ps) or min(sc, ps) <= 0 or max(sc, ps) >= 2 ** 31:
+            return None
+        return sc, ps
+
+    def head_loss(self, centernesses, bbox_preds, cls_scores, valids, points, centerness_targets, bbox_targets, labels, rotated,
+                  gamma=2.0, alpha=0.25, loss_weights=(1.0, 1.0, 1.0), n_pos_override=None):
+        """``ImVoxelHeadV2._loss_single`` for one image in two launches (three for the rotated head), ``sgc_head_loss_forward``: per
+        scale centerness [1,X,Y,Z], bbox_pred [6|7,X,Y,Z] (activated), cls_score [C,X,Y,Z] (read in place when their points lie at a
+        constant stride), valid [X*Y*Z] bool / uint8; points [n,3] and the outputs of ``assign_targets`` for them ->
+        (losses [3] = centerness, bbox, cls; n_pos [1], the local count; state).  ``state`` holds the unnormalised gradients and what
+        ``head_loss_grads`` / ``head_loss_finalize`` need.  ``n_pos_override``: 1-element device tensor or None."""
+        import struct
+        from ._abi import HEAD_LOSS_MAX_SCALES
+        n_scales = len(centernesses)
+        if not (n_scales == len(bbox_preds) == len(cls_scores) == len(valids)) or n_scales == 0:
+            raise RuntimeError("head_loss: one centerness, bbox_pred, cls_score and valid tensor per scale expected")
+        self._check(points=points, centerness_targets=centerness_targets, bbox_targets=bbox_targets, labels=labels,
+                    n_pos_override=n_pos_override)
+        self._f32(points=points, centerness_targets=centerness_targets, bbox_targets=bbox_targets, n_pos_override=n_pos_override)
+        self._i64(labels=labels)
+        n = points.shape[0]
+        n_reg, n_classes = bbox_preds[0].shape[0], cls_scores[0].shape[0]
+        if points.shape != (n, 3) or centerness_targets.shape != (n,) or bbox_targets.shape != (n, n_reg) or labels.shape != (n,):
+            raise RuntimeError("head_loss: points [n,3], centerness_targets [n], bbox_targets [n,n_reg], labels [n] expected")
+        if n_pos_override is not None and n_pos_override.numel() != 1:
+            raise RuntimeError("head_loss: n_pos_override holds one float")
+        if n_scales > HEAD_LOSS_MAX_SCALES or n_reg not in (6, 7) or bool(rotated) != (n_reg == 7):
+            raise RuntimeError(f"head_loss: unsupported: {n_scales} scales (at most {HEAD_LOSS_MAX_SCALES}), n_reg = {n_reg} "
+                               f"(6, or 7 with rotated), rotated = {bool(rotated)}")
+        dev, keep, blob, shapes = points.device, [], b"", []
+        for l, (ctr, reg, cls, val) in enumerate(zip(centernesses, bbox_preds, cls_scores, valids)):
+            grid = tuple(ctr.shape[1:])
+            if ctr.dim() != 4 or ctr.shape[0] != 1 or tuple(reg.shape) != (n_reg,) + grid or tuple(cls.shape) != (n_classes,) + grid:
+                raise RuntimeError(f"head_loss: scale {l}: centerness [1,X,Y,Z], bbox_pred [{n_reg},X,Y,Z], cls_score [{n_classes},X,Y,Z] expected")
+            n_l = grid[0] * grid[1] * grid[2]
+            if val.numel() != n_l or val.dtype not in (torch.bool, torch.uint8):
+                raise RuntimeError(f"head_loss: scale {l}: valid must hold {n_l} bool / uint8 values")
+            row = []
+            for name, t in (("centerness", ctr), ("bbox_pred", reg), ("cls_score", cls)):
+                if t.device != dev:
+                    raise RuntimeError(f"head_loss: scale {l}: {name} is on {t.device}, expected {dev}")
+                self._f32(**{name: t})
+                st = self._point_strides(t)
+                if st is None:
+                    t = t.contiguous()
+                    st = (n_l, 1)
+                keep.append(t)
+                row.append((t.data_ptr(), st))
+            val = val.contiguous().view(torch.uint8)
+            self._check(valid=val)
+            keep.append(val)
+            blob += struct.pack("<4Qq6i", row[0][0], row[1][0], row[2][0], val.data_ptr(), n_l, row[0][1][1], row[1][1][0], row[1][1][1],
+                                row[2][1][0], row[2][1][1], 0)
+            shapes.append(grid)
+        if sum(g[0] * g[1] * g[2] for g in shapes) != n:
+            raise RuntimeError("head_loss: the scales hold another number of points than the point list")
+        nbytes = int(self.lib._dll.sgc_head_loss_workspace_bytes(n, n_scales))
+        ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+        losses = torch.empty(3, dtype=torch.float32, device=dev)
+        n_pos = torch.empty(1, dtype=torch.float32, device=dev)
+        grads = torch.empty((1 + n_reg + n_classes) * n, dtype=torch.float32, device=dev)
+        lw = tuple(float(x) for x in loss_weights)
+        self._call("sgc_head_loss_forward", blob, n_scales, points, centerness_targets, bbox_targets, labels, n, n_reg, n_classes,
+                   int(bool(rotated)), float(gamma), float(alpha), lw[0], lw[1], lw[2], n_pos_override, losses, n_pos, grads, ws, nbytes)
+        del keep
+        return losses, n_pos, dict(grads=grads, workspace=ws, shapes=shapes, n_reg=n_reg, n_classes=n_classes, loss_weights=lw)
+
+    @staticmethod
+    def _level_points(state):
+        import ctypes
+        return (ctypes.c_int64 * len(state["shapes"]))(*[g[0] * g[1] * g[2] for g in state["shapes"]])
+
+    def head_loss_finalize(self, state, n_pos_override):
+        """Losses and scale factors of a ``head_loss`` call again, normalised by ``n_pos_override`` (1-element device tensor; a
+        distributed run's all-reduced mean) -> (losses [3], n_pos [1], still the local count).  One launch."""
+        self._check(n_pos_override=n_pos_override)
+        self._f32(n_pos_override=n_pos_override)
+        ws, lw = state["workspace"], state["loss_weights"]
+        losses = torch.empty(3, dtype=torch.float32, device=ws.device)
+        n_pos = torch.empty(1, dtype=torch.float32, device=ws.device)
+        self._call("sgc_head_loss_finalize", ws, ws.numel() * 8, self._level_points(state), len(state["shapes"]), n_pos_override,
+                   lw[0], lw[1], lw[2], losses, n_pos)
+        return losses, n_pos
+
+    def head_loss_grads(self, state, grad_centerness, grad_bbox, grad_cls):
+        """The gradients of ``sum_k grad_k * losses[k]`` with respect to the head tensors of a ``head_loss`` call, one launch
+        (``sgc_head_loss_scale_grads``): three 1-element device tensors -> (centerness grads, bbox_pred grads, cls_score grads), each a
+        list of [C,X,Y,Z] tensors per scale (views of one buffer)."""
+        gs = dict(grad_centerness=grad_centerness, grad_bbox=grad_bbox, grad_cls=grad_cls)
+        self._check(**gs)
+        self._f32(**gs)
+        if any(g.numel() != 1 for g in gs.values()):
+            raise RuntimeError("head_loss_grads: one upstream gradient per loss expected")
+        stash, n_reg, n_classes = state["grads"], state["n_reg"], state["n_classes"]
+        out = torch.empty_like(stash)
+        self._call("sgc_head_loss_scale_grads", stash, out, self._level_points(state), len(state["shapes"]), n_reg, n_classes,
+                   state["workspace"], grad_centerness, grad_bbox, grad_cls)
+        ctr, reg, cls, at = [], [], [], 0
+        for X, Y, Z in state["shapes"]:
+            n_l = X * Y * Z
+            level = out[at:at + (1 + n_reg + n_classes) * n_l].view(1 + n_reg + n_classes, X, Y, Z)
+            ctr.append(level[:1])
+            reg.append(level[1:1 + n_reg])
+            cls.append(level[1 + n_reg:])
+            at += (1 + n_reg + n_classes) * n_l
+        return ctr, reg, cls
+
     def unpack_conv_wgrad(self, dw_trc, shape, transpose=False, flip=False):
         """[T, R, C] fp32 (``conv3d_wgrad_bf16x3``) -> the parameter's layout ``shape`` = [A, B, *taps] (``sgc_unpack_conv_wgrad``)."""
         self._check(dw_trc=dw_trc)

@@ -21,6 +21,9 @@ ap.add_argument("--sites", action="store_true", help="torch ops of one step by t
 ap.add_argument("--optimizer", default="none", choices=["none", "torch", "fused"],
                 help="the parameter update after the backward: none (forward + backward only), torch (clip_grad_norm_(35) + torch.optim.AdamW over "
                      "the reference's groups, foreach and fused=True both timed, the faster one reported) or fused (sgcdet_amd.optim.FusedAdamW)")
+ap.add_argument("--real-loss", action="store_true",
+                help="train against forward_train_from_features with 30 seeded boxes (target assignment + the head's three losses + the "
+                     "occupancy loss) instead of the dummy quadratic loss; SGC_HEAD_LOSS_FUSED=0 / 1 selects the torch / fused head loss")
 ap.add_argument("--glue", action="store_true", help="attribute the torch glue ops (copy / add / fill / sum / mul ...) to source lines of this package")
 args = ap.parse_args()
 w = workload(args.workload)
@@ -33,6 +36,12 @@ if args.input_layout == "nhwc":         # same logical [1, N, C, H, W] tensors, 
 feats = [f.requires_grad_(True) for f in feats]
 dpt = dpt.requires_grad_(True)
 params = [p for p in det.parameters() if p.requires_grad]
+if args.real_loss:
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    from targets_contract import random_boxes
+    rotated = w.get("head") == "SunRgbdImVoxelHeadV2"
+    gt_boxes, gt_labels = random_boxes(30, 4, rotated)
+    gt_boxes, gt_labels = gt_boxes.cuda(), (gt_labels % w["n_classes"]).cuda()
 
 update = [None]      # the parameter update of --optimizer, called after the backward
 
@@ -44,6 +53,8 @@ def step():
         dpts = [dpt, F.interpolate(dpt, scale_factor=(1, 0.5, 0.5), mode="nearest"), F.interpolate(dpt, scale_factor=(1, 0.25, 0.25), mode="nearest")]
         vol, valid, occ = det.voxel_head(feats, meta, dpts)
         loss = (vol ** 2).mean() + occ.mean()
+    elif args.real_loss:
+        loss = sum(det.forward_train_from_features(feats, [meta], dpt, [gt_boxes], [gt_labels]).values())
     else:
         r = det.forward_features(feats, [meta], dpt)
         loss = sum((t ** 2).mean() for k in ("centerness", "bbox_pred", "cls_score") for t in r[k]) + r["occ"].mean()
