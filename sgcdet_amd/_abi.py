@@ -5,7 +5,9 @@ One table drives every binding of that header: the product library
 only -- the CPU oracle that exports the same symbols.  The training-only entry
 points of ``include/sgcdet_amd_train.h`` have a table of their own
 (``TRAIN_SIGNATURES`` / ``TRAIN_INTROSPECTION``), bound only when ``Library`` is
-asked for it (the product library; the oracle has no twin of them).  Nothing
+asked for it (the product library; the oracle has no twin of them); the image-side
+convolutions of ``include/sgcdet_amd_image.h`` likewise (``IMAGE_SIGNATURES`` /
+``IMAGE_INTROSPECTION``).  Nothing
 here touches torch; pointers are plain integers (``tensor.data_ptr()``).
 """
 import ctypes as C
@@ -115,6 +117,19 @@ TRAIN_INTROSPECTION = {
     "sgc_head_loss_workspace_bytes": (C.c_int64, [_i] * 2),
 }
 
+# include/sgcdet_amd_image.h: the 2-D convolutions of the image-side CNNs (no CPU-oracle twin)
+IMAGE_SIGNATURES = {
+    "sgc_conv2d_nhwc_ex_bf16x3": [_p] * 7 + [_i] * 13 + [_p],
+    "sgc_conv2d_stem7_bf16x3": [_p] * 6 + [_i] * 4 + [_p],
+    "sgc_nchw_to_nhwc_padc": [_p, _p] + [_i] * 5 + [_p],
+}
+
+IMAGE_INTROSPECTION = {
+    "sgc_conv2d_nhwc_ex_supported": (C.c_int, [_i] * 12),
+}
+
+CONV2D_RELU, CONV2D_RELU_AFTER_ADD = 1, 2      # SGC_CONV2D_* flags of include/sgcdet_amd_image.h
+
 
 class OptimGroup(C.Structure):
     """``sgc_optim_group`` of include/sgcdet_amd_train.h: the hyper-parameters of one parameter group, as Python floats."""
@@ -135,13 +150,14 @@ class SgcError(RuntimeError):
 class Library:
     """A loaded shared object exporting the sgcdet_amd C ABI."""
 
-    def __init__(self, path, train=False):
-        """``train``: also bind (and require) the entry points of include/sgcdet_amd_train.h."""
+    def __init__(self, path, train=False, image=False):
+        """``train`` / ``image``: also bind (and require) the entry points of include/sgcdet_amd_train.h /
+        include/sgcdet_amd_image.h."""
         self.path = str(path)
         self._dll = C.CDLL(self.path)
         missing = []
-        signatures = {**SIGNATURES, **TRAIN_SIGNATURES} if train else SIGNATURES
-        introspection = {**INTROSPECTION, **TRAIN_INTROSPECTION} if train else INTROSPECTION
+        signatures = {**SIGNATURES, **(TRAIN_SIGNATURES if train else {}), **(IMAGE_SIGNATURES if image else {})}
+        introspection = {**INTROSPECTION, **(TRAIN_INTROSPECTION if train else {}), **(IMAGE_INTROSPECTION if image else {})}
         for name, argtypes in signatures.items():
             try:
                 fn = getattr(self._dll, name)

@@ -28,7 +28,7 @@ def library():
                     f"sgcdet_amd: {path} is missing and could not be built ({e}). "
                     "Run `python -m sgcdet_amd.build` (needs hipcc, targets gfx950). "
                     "There is no CPU fallback for the product path.") from e
-        _LIB = Library(path, train=True)
+        _LIB = Library(path, train=True, image=True)
         if _LIB.backend != "hip-gfx950":
             raise ImportError(f"sgcdet_amd: {path} reports backend '{_LIB.backend}', expected 'hip-gfx950'")
     return _LIB

@@ -3,7 +3,9 @@
 Reference: mmdet3d_plugin/models/detectors/SGCDet.py:61-129.  The 2D backbone (ResNet + FPN, mmdet -- not in the
 reference tree) is upstream of the path and is NOT built here: its configs are accepted and kept.  ``depth_head``
 (``DepthNet_Fusion``, row f-2 of SURVEY.md section 8) IS built when configured: ``build_volume_from_fpn`` runs it on the
-finest FPN map + the images (SGCDet.py:71-85) and hands its depth distribution to the path.  The path itself starts
+finest FPN map + the images (SGCDet.py:71-85) and hands its depth distribution to the path -- in inference on the GPU its
+2-D CNNs run on the library's MFMA kernels and the distribution is channels-last in memory (plugin/depth_net.py), which
+``depth_pyramid`` keeps zero-copy.  The path itself starts
 from FPN maps ``x[l] = [1,N,C,H_l,W_l]`` and the depth distribution ``[1,N,D,H_0,W_0]``:
 
     volume, valid, occ = voxel_head(x, img_metas[0], mlvl_dpt_dists)      # SGCDet.py:87

@@ -3,8 +3,9 @@ is the same kernel family as the hot path.
 
 Reference: mmdet3d_plugin/models/im2voxel/depth_utils/depth_est_fusion.py -- ``get_closest_frame_ids`` (:53-64),
 ``collect_proj`` (:67-84), ``homo_warping`` (:87-126) and the cost-volume loop of ``DepthNet_Fusion.forward``
-(:203-240).  The 2-D CNNs around it (``ResNetFPN``, ``SimpleUnet2D``) are dense library convolutions and are not
-built here.  ``plane_sweep_correlation`` takes what ``forward`` has at :222 (matching features + ``img_meta``) and
+(:203-240).  The 2-D CNNs around it (``ResNetFPN``, ``SimpleUnet2D``) run on the library's MFMA kernels in inference
+(plugin/depth_net.py ``_forward_hip``: the extractor hands over channels-last features, which the zero-copy branch below
+reads in place) and on torch's convolutions under autograd; they are not built here.  ``plane_sweep_correlation`` takes what ``forward`` has at :222 (matching features + ``img_meta``) and
 returns what it has at :240 (``correlation``), computed by ``sgc_plane_sweep_corr`` without materialising the warped
 neighbour features [N, C, D, H, W].  Under autograd the same call is differentiable with respect to the matching
 features (``functions.PlaneSweepCorrFunction``: backward ``sgc_plane_sweep_corr_backward``).

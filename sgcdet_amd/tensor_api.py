@@ -803,6 +803,80 @@ class TensorOps:
                    _meta=dict(V=rows, Cin=Cin, Cout=Cout, taps=taps, OV=rows))
         return y
 
+    # ---- 7b. image-side 2-D convolutions (include/sgcdet_amd_image.h) --------------------------------
+    def conv2d_nhwc_ex_supported(self, nhw, Cin, Cout, ksize, stride=1, transposed=False, ldy=None, col0=0, ldr=0, softmax_cols=0):
+        """``ldr``: row pitch of the residual, 0 without one."""
+        N, H, W = nhw
+        return bool(self.lib._dll.sgc_conv2d_nhwc_ex_supported(N, H, W, Cin, Cout, ksize, stride, int(transposed),
+                                                               Cout if ldy is None else ldy, col0, ldr, softmax_cols))
+
+    def conv2d_nhwc_ex_bf16x3(self, x, w_hi, w_lo, nhw, ksize, stride=1, transposed=False, scale=None, shift=None,
+                              residual=None, relu=False, relu_after_add=False, out=None, col0=0, softmax_cols=0):
+        """Strided / transposed 2-D convolution over channels-last rows (``sgc_conv2d_nhwc_ex_bf16x3``): x [N*H*W, Cin] ->
+        [N*OH*OW, Cout]; k in {1,3} stride in {1,2} padding k//2, or ``transposed`` = ConvTranspose2d(3, stride 2, padding 1,
+        output_padding 1).  Weights [k*k, Cout, Cin] split as ``split_operand``.  Epilogue: scale/shift, ``relu``,
+        + ``residual`` [rows, >= Cout] (its own row pitch), ``relu_after_add``, softmax over the first ``softmax_cols`` columns.
+        ``out`` [rows, ldy] with ``col0``: the Cout columns land at [col0, col0 + Cout), the others are not touched."""
+        self._check(x=x, w_hi=w_hi, w_lo=w_lo, scale=scale, shift=shift, residual=residual, out=out)
+        self._f32(x=x, scale=scale, shift=shift, residual=residual, out=out)
+        if w_hi.dtype != torch.bfloat16 or w_lo.dtype != torch.bfloat16 or w_hi.shape != w_lo.shape:
+            raise RuntimeError("conv2d_nhwc_ex_bf16x3: w_hi / w_lo must be bfloat16 tensors of one shape")
+        N, H, W = nhw
+        rows, Cin = x.shape
+        taps, Cout, Cin2 = w_hi.shape
+        if transposed and (ksize != 3 or stride != 2):
+            raise RuntimeError("conv2d_nhwc_ex_bf16x3: the transposed form is 3x3 stride 2")
+        if rows != N * H * W or Cin2 != Cin or taps != ksize * ksize or stride not in (1, 2):
+            raise RuntimeError("conv2d_nhwc_ex_bf16x3: inconsistent shapes")
+        if not transposed and stride == 2 and (H % 2 or W % 2):
+            raise RuntimeError("conv2d_nhwc_ex_bf16x3: a stride-2 layer needs even H and W")
+        OH, OW = (2 * H, 2 * W) if transposed else (H // stride, W // stride)
+        orows = N * OH * OW
+        y = out if out is not None else torch.empty((orows, Cout), dtype=torch.float32, device=x.device)
+        if y.dim() != 2 or y.shape[0] != orows or col0 < 0 or col0 + Cout > y.shape[1]:
+            raise RuntimeError("conv2d_nhwc_ex_bf16x3: bad `out` shape / column offset")
+        if residual is not None and (residual.dim() != 2 or residual.shape[0] != orows or residual.shape[1] < Cout):
+            raise RuntimeError("conv2d_nhwc_ex_bf16x3: bad residual shape")
+        for name, v in (("scale", scale), ("shift", shift)):
+            if v is not None and v.numel() != Cout:
+                raise RuntimeError(f"conv2d_nhwc_ex_bf16x3: {name} must have Cout elements")
+        if not 0 <= softmax_cols <= Cout:
+            raise RuntimeError("conv2d_nhwc_ex_bf16x3: softmax_cols outside [0, Cout]")
+        flags = (1 if relu else 0) | (2 if relu_after_add else 0)
+        self._call("sgc_conv2d_nhwc_ex_bf16x3", x, w_hi, w_lo, scale, shift, residual, y, N, H, W, Cin, Cout, ksize, stride,
+                   int(transposed), flags, y.shape[1], col0, residual.shape[1] if residual is not None else 0, softmax_cols,
+                   _meta=dict(V=rows, Cin=Cin, Cout=Cout, taps=taps, OV=orows, stride=stride, transposed=bool(transposed)))
+        return y
+
+    def conv2d_stem7_bf16x3(self, img, w_hi, w_lo, scale=None, shift=None, relu=True):
+        """fp32 NCHW images [N, 3, H, W] -> channels-last rows [N*(H/2)*(W/2), 64] of the 7x7 stride-2 padding-3 stem
+        (``sgc_conv2d_stem7_bf16x3``); weights [64, 160] split planes, column (ci*7 + kh)*7 + kw, zero tail."""
+        self._check(img=img, w_hi=w_hi, w_lo=w_lo, scale=scale, shift=shift)
+        self._f32(img=img, scale=scale, shift=shift)
+        if w_hi.dtype != torch.bfloat16 or w_lo.dtype != torch.bfloat16 or w_hi.shape != (64, 160) or w_lo.shape != (64, 160):
+            raise RuntimeError("conv2d_stem7_bf16x3: w_hi / w_lo must be bfloat16 [64, 160]")
+        if img.dim() != 4 or img.shape[1] != 3 or img.shape[2] % 2 or img.shape[3] % 2:
+            raise RuntimeError("conv2d_stem7_bf16x3: img must be [N, 3, H, W] with even H and W")
+        for name, v in (("scale", scale), ("shift", shift)):
+            if v is not None and v.numel() != 64:
+                raise RuntimeError(f"conv2d_stem7_bf16x3: {name} must have 64 elements")
+        N, _, H, W = img.shape
+        y = torch.empty((N * (H // 2) * (W // 2), 64), dtype=torch.float32, device=img.device)
+        self._call("sgc_conv2d_stem7_bf16x3", img, w_hi, w_lo, scale, shift, y, N, H, W, int(relu),
+                   _meta=dict(V=y.shape[0], Cin=147, Cout=64, taps=1, OV=y.shape[0]))
+        return y
+
+    def nchw_to_nhwc_padc(self, src, Cp):
+        """[N, C, H, W] contiguous -> rows [N*H*W, Cp] with zero columns behind C (``sgc_nchw_to_nhwc_padc``)."""
+        self._check(src=src)
+        self._f32(src=src)
+        if src.dim() != 4 or Cp < src.shape[1] or Cp % 4:
+            raise RuntimeError("nchw_to_nhwc_padc: src [N,C,H,W], Cp >= C, Cp % 4 == 0")
+        N, Cc, H, W = src.shape
+        dst = torch.empty((N * H * W, Cp), dtype=torch.float32, device=src.device)
+        self._call("sgc_nchw_to_nhwc_padc", src, dst, N, Cc, H, W, Cp)
+        return dst
+
     def pack_conv_weight(self, w, transpose=False, flip=False, pad_rows=1, pad_cols=1, out=None):
         """Module parameter [A, B, *taps] (Conv3d [Cout, Cin, k, k, k], ConvTranspose3d [Cin, Cout, 2, 2, 2], Linear [Cout, Cin])
         -> (hi, lo) bf16 [T, R, C] in the kernels' layout: rows = A (or B with ``transpose``), taps mirrored with ``flip``,
