@@ -21,7 +21,7 @@ from torch import nn
 
 from .. import ext
 from ..mmcv_lite import HEADS, LOSSES, Scale, bias_init_with_prob, multi_apply, normal_init
-from .conv_plan import train_conv_on_hip, ConvSpec, module_fingerprint, rows_to_ncdhw, to_channels_last_rows
+from .conv_plan import train_conv_on_hip, ConvSpec, cached_plan, rows_to_ncdhw, to_channels_last_rows
 from . import losses  # registers the LOSSES entries the head builds
 
 
@@ -74,24 +74,19 @@ class ImVoxelHeadV2(nn.Module):
         normal_init(self.reg_conv, std=0.01)
         normal_init(self.cls_conv, std=0.01, bias=bias_init_with_prob(0.01))
 
-    def _plan(self):
+    def _build_plan(self):
         """The three 3x3x3 convolutions share their input: one fused conv with
         Cout = 1 + n_reg + n_classes (centerness | reg | cls) on the MFMA kernel."""
-        fp = module_fingerprint(self)
-        if getattr(self, "_hip_plan", None) is not None and self._hip_plan[0] == fp:
-            return self._hip_plan[1]
         w = torch.cat([self.centerness_conv.weight, self.reg_conv.weight, self.cls_conv.weight], 0)
         n_reg = self.reg_conv.weight.shape[0]
         bias = torch.cat([self.cls_conv.bias.new_zeros(1 + n_reg), self.cls_conv.bias])
-        spec = ConvSpec(w, None, bias=bias, ksize=3, pad_out=False)
-        self._hip_plan = (fp, (spec, n_reg))
-        return self._hip_plan[1]
+        return ConvSpec(w, None, bias=bias, ksize=3, pad_out=False), n_reg
 
     def _forward_hip(self, feats, valid_masks=None):
         """``valid_masks``: per scale a uint8 [X*Y*Z] mask (the head's own valid pyramid, :123,258): the tensors are only
         consumed there (scores are multiplied by it, :301), so the convolution may skip tiles without a valid voxel."""
         from .conv_plan import CONV_MODE
-        spec, n_reg = self._plan()
+        spec, n_reg = cached_plan(self, self._build_plan)
         ctr, reg, cls = [], [], []
         # exp(scale(reg)) of the box distances (:79,110; the first 6 regression outputs of either head class) runs in the
         # convolution's epilogue on the MFMA path -- no elementwise launches; the strict-fp32 convolution keeps the torch ops

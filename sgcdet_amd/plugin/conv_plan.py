@@ -1,10 +1,14 @@
-"""Eval-mode lowering of the neck / head convolution chains onto ``sgc_conv3d_cl_f32``.
+"""What the eval-mode lowerings of the plugin modules share: a module's layers prepared once for the library's kernels.
 
-BatchNorm3d (running statistics) is folded into a per-channel scale/shift applied in the
-kernel's epilogue, weights are permuted once to the kernel's ``[tap][Cout][Cin]`` layout, and
-channel counts are zero-padded to multiples of 32 (the K tile) -- a no-op for every SGCDet
-config (128 ... 1024 channels).  Plans are cached per module and rebuilt when a parameter or
-buffer changes (``Tensor._version``) or moves device.
+``ConvSpec`` (3-D: neck and head, ``sgc_conv3d_cl_*`` / Winograd-z), ``Conv2dSpec`` (2-D: FPN and depth net,
+``sgc_conv2d_nhwc_bf16x3`` / ``sgc_conv2d_nhwc_ex_bf16x3``), ``LinearSpec`` and ``BlockDiagSpec`` (the row GEMMs of the
+transformer) each hold one layer as the kernels take it and dispatch it in ``__call__``.  Eval BatchNorm (running statistics)
+and the bias are folded into a per-channel scale / shift for the kernel's epilogue (``fold_norm``, the only copy), weights are
+permuted once to ``[tap][Cout][Cin]``, and channel counts are zero-padded to multiples of 32 (the K tile; ``_pad_to``) with zero
+weight rows, scale 1 and shift 0, so padded output columns are exactly 0.  ``cached_plan`` keeps a module's plan and rebuilds it
+when ``module_fingerprint`` changes: a parameter or buffer was updated in place (``Tensor._version``) or moved, or the
+arithmetic mode was switched.  ``image_rows`` / ``to_channels_last_rows`` bring NCHW / NCDHW tensors to the channels-last rows
+the kernels read.  The process-wide switches (arithmetic mode, Winograd-z, throughput geometry, training path) live here too.
 """
 import os
 
@@ -62,6 +66,19 @@ def _pad_to(n, m=_PAD):
     return (n + m - 1) // m * m
 
 
+def fold_norm(cout, bn=None, bias=None, device=None):
+    """(scale, shift) [cout] of a convolution's epilogue: eval BatchNorm ``y = (x - mean) / sqrt(var + eps) * gamma + beta``
+    behind it with the convolution's bias folded in; without a norm: (1, bias)."""
+    if bn is None:
+        shift = bias.detach().float() if bias is not None else torch.zeros(cout, dtype=torch.float32, device=device)
+        return torch.ones(cout, dtype=torch.float32, device=device), shift
+    scale = bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)
+    shift = bn.bias.detach().float() - bn.running_mean.detach().float() * scale
+    if bias is not None:
+        shift = shift + bias.detach().float() * scale
+    return scale, shift
+
+
 class ConvSpec:
     """One prepared convolution: wt [taps, Cout_p, Cin_p], scale/shift [Cout_p]."""
 
@@ -79,12 +96,7 @@ class ConvSpec:
         wp[:, :cout, :cin] = wt
         scale = torch.ones(cout_p, dtype=torch.float32, device=w.device)
         shift = torch.zeros(cout_p, dtype=torch.float32, device=w.device)
-        if bn is not None:                   # y = (x - mean) / sqrt(var + eps) * gamma + beta
-            s = bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)
-            scale[:cout] = s
-            shift[:cout] = bn.bias.detach().float() - bn.running_mean.detach().float() * s
-        if bias is not None:
-            shift[:cout] += bias.detach().float() * scale[:cout]
+        scale[:cout], shift[:cout] = fold_norm(cout, bn, bias, w.device)
         self.wt, self.scale, self.shift = wp.contiguous(), scale, shift
         self.w_hi, self.w_lo = ext.ops().split_operand(self.wt) if w.is_cuda else (None, None)
         self.cin, self.cout, self.cin_p, self.cout_p = cin, cout, cin_p, cout_p
@@ -127,6 +139,53 @@ class ConvSpec:
             raise NotImplementedError("the output activation lives in the bf16x3 convolution's epilogue")
         return ext.ops().conv3d_cl(x, self.wt, grid, self.ksize, self.stride, self.transposed, self.scale,
                                    self.shift, residual, relu)
+
+
+class Conv2dSpec:
+    """One prepared 2-D convolution, the twin of ``ConvSpec`` for image rows: w [k*k, Cout_p, Cin_p] (tap = kh*k + kw, rows =
+    output channels; a ConvTranspose2d's [Cin, Cout, k, k] parameter is transposed, not flipped: the kernel sums by output
+    parity), scale / shift [Cout_p].  Channels are reordered by ``in_perm`` / ``out_perm`` (new index -> module index), then
+    zero-padded to a multiple of 32 (``pad_in`` / ``pad_out`` = False: that dimension stays as it is), so the padded output
+    columns of every layer are exactly 0 (zero weight rows, scale 1, shift 0).  ``unit_scale=False``: a layer without a norm
+    has ``scale = None`` (the kernels' own no-scale epilogue) instead of a vector of ones."""
+
+    def __init__(self, conv, bn=None, in_perm=None, out_perm=None, pad_in=True, pad_out=True, unit_scale=True):
+        self.transposed = isinstance(conv, torch.nn.ConvTranspose2d)
+        w = conv.weight.detach().float()
+        w = w.permute(2, 3, 1, 0) if self.transposed else w.permute(2, 3, 0, 1)          # [k, k, Cout, Cin]
+        scale, shift = fold_norm(w.shape[2], bn, conv.bias, w.device)
+        if in_perm is not None:
+            w = w[..., in_perm]
+        if out_perm is not None:
+            w, scale, shift = w[:, :, out_perm], scale[out_perm], shift[out_perm]
+        k, _, cout, cin = w.shape
+        dout, din = (_pad_to(cout) - cout if pad_out else 0), (_pad_to(cin) - cin if pad_in else 0)
+        pad = torch.nn.functional.pad
+        self.scale = pad(scale, (0, dout), value=1.0).contiguous() if bn is not None or unit_scale else None
+        self.shift = pad(shift, (0, dout)).contiguous()
+        self.k, self.stride, self.cin, self.cout = k, conv.stride[0], cin, cout
+        self.set_weight(pad(w.reshape(k * k, cout, cin), (0, din, 0, dout)).contiguous())
+
+    def set_weight(self, w):
+        """``w`` as the entry point reads it; its operand planes are split where the kernels run (a plan stays constructible on the CPU)."""
+        self.w = w
+        self.w_hi, self.w_lo = ext.ops().split_operand(w) if w.is_cuda else (None, None)
+
+    def __call__(self, x, nhw, residual=None, relu=True, relu_after_add=False, out=None, col0=0, softmax_cols=0):
+        """The layer on rows ``x``; returns (rows, (N, OH, OW)).  Plain stride-1 layers go to the halo form of
+        ``sgc_conv2d_nhwc_bf16x3`` (its `relu = 2`: ReLU, then the skip), everything else to ``sgc_conv2d_nhwc_ex_bf16x3``."""
+        ops = ext.ops()
+        N, H, W = nhw
+        onhw = (N, 2 * H, 2 * W) if self.transposed else (N, H // self.stride, W // self.stride)
+        if (self.stride == 1 and not self.transposed and out is None and not relu_after_add and softmax_cols == 0
+                and (residual is None or residual.shape[1] == self.w_hi.shape[1])):
+            mode = (2 if residual is not None else 1) if relu else 0
+            return ops.conv2d_nhwc_bf16x3(x, self.w_hi, self.w_lo, nhw, self.k, scale=self.scale, shift=self.shift,
+                                          residual=residual, relu=mode), onhw
+        y = ops.conv2d_nhwc_ex_bf16x3(x, self.w_hi, self.w_lo, nhw, self.k, stride=self.stride, transposed=self.transposed,
+                                      scale=self.scale, shift=self.shift, residual=residual, relu=relu,
+                                      relu_after_add=relu_after_add, out=out, col0=col0, softmax_cols=softmax_cols)
+        return y, onhw
 
 
 # training / autograd path of the neck and head convolutions: "hip" = forward, input and weight gradients on the MFMA
@@ -245,6 +304,26 @@ def module_fingerprint(module):
         module.__dict__["_fp_tensors"] = tensors
         module.__dict__["_fp_training"] = module.training
     return (CONV_PRODUCTS,) + tuple((t.data_ptr(), t._version) for t in tensors)       # a mode switch rebuilds the weight planes
+
+
+def cached_plan(module, build, attr="_hip_plan", fingerprint=None):
+    """``module``'s prepared plan: the one stored under ``module.__dict__[attr]`` while ``fingerprint`` (default:
+    ``module_fingerprint(module)``) is the one it was built at, else ``build()``, stored.  Popping the attribute forces a rebuild."""
+    fp = module_fingerprint(module) if fingerprint is None else fingerprint
+    cached = module.__dict__.get(attr)
+    if cached is not None and cached[0] == fp:
+        return cached[1]
+    plan = build()
+    module.__dict__[attr] = (fp, plan)
+    return plan
+
+
+def image_rows(x):
+    """[N, C, H, W] (any strides) -> ([N*H*W, C] fp32 rows, (N, H, W)); zero-copy for channels-last fp32 memory."""
+    N, C, H, W = x.shape
+    if x.is_contiguous(memory_format=torch.channels_last) and x.dtype == torch.float32:
+        return x.permute(0, 2, 3, 1).reshape(N * H * W, C), (N, H, W)
+    return ext.ops().nchw_to_nhwc_crop(x.float(), H, W).view(N * H * W, C), (N, H, W)
 
 
 def to_channels_last_rows(x):

@@ -34,7 +34,7 @@ import torch.nn.functional as F
 
 from .. import ext
 from ..mmcv_lite import HEADS
-from .conv_plan import module_fingerprint
+from .conv_plan import Conv2dSpec, cached_plan, image_rows
 from .plane_sweep import closest_frame_ids, plane_sweep_correlation
 
 
@@ -182,80 +182,34 @@ def homo_warping(src_fea, src_proj, ref_proj, depth_values):
 HIP_DEFAULT = "1"      # SGC_DEPTH_NET_HIP when the environment does not set it (DESIGN.md 4.10 says how it was chosen)
 
 
-# ---- the eval-mode plan of the 2-D CNNs: folded, padded, permuted layers as plain tensors (device of the module) --------------
-def _pad32(c):
-    return (c + 31) // 32 * 32
-
-
-def _fold(conv, bn):
-    """(scale, shift) [Cout] of eval BatchNorm after ``conv`` (bias folded in); without a norm: (1, bias)."""
-    cout = conv.out_channels
-    bias = conv.bias.detach().float() if conv.bias is not None else torch.zeros(cout, device=conv.weight.device)
-    if bn is None:
-        return torch.ones(cout, device=conv.weight.device), bias
-    scale = bn.weight.detach().float() / torch.sqrt(bn.running_var.float() + bn.eps)
-    return scale, bn.bias.detach().float() - bn.running_mean.float() * scale + bias * scale
-
-
-def _layer(conv, bn=None, in_perm=None, out_perm=None, pad_out=True):
-    """One convolution as the kernels take it: w [k*k, Cout_p, Cin_p] (tap = kh*k + kw, rows = output channels; a
-    ConvTranspose2d's [Cin, Cout, k, k] parameter is transposed, not flipped: the kernel sums by output parity), scale /
-    shift [Cout_p].  Channels are reordered by ``in_perm`` / ``out_perm`` (new index -> module index), then BOTH dimensions
-    are zero-padded to a multiple of 32 (``pad_out=False``: the output stays as it is), so the padded output columns of every
-    layer are exactly 0 (zero weight rows, scale 1, shift 0)."""
-    transposed = isinstance(conv, nn.ConvTranspose2d)
-    w = conv.weight.detach().float()
-    w = w.permute(2, 3, 1, 0) if transposed else w.permute(2, 3, 0, 1)          # [k, k, Cout, Cin]
-    scale, shift = _fold(conv, bn)
-    if in_perm is not None:
-        w = w[..., in_perm]
-    if out_perm is not None:
-        w, scale, shift = w[:, :, out_perm], scale[out_perm], shift[out_perm]
-    k, _, cout, cin = w.shape
-    coutp, cinp = (_pad32(cout) if pad_out else cout), _pad32(cin)
-    w = F.pad(w.reshape(k * k, cout, cin), (0, cinp - cin, 0, coutp - cout))
-    return dict(w=w.contiguous(), scale=F.pad(scale, (0, coutp - cout), value=1.0).contiguous(),
-                shift=F.pad(shift, (0, coutp - cout)).contiguous(), k=k, stride=conv.stride[0], transposed=transposed,
-                cin=cin, cout=cout)
-
-
+# ---- the eval-mode plan of the 2-D CNNs: folded, padded, permuted layers (``Conv2dSpec``, on the device of the module) ---------
 def _unet_layers(u, in_perm=None, out_perm=None):
-    return dict(conv1=_layer(u.conv1.conv, u.conv1.bn, in_perm=in_perm), conv2=_layer(u.conv2.conv, u.conv2.bn),
-                conv3=_layer(u.conv3.conv, u.conv3.bn), conv4=_layer(u.conv4.conv, u.conv4.bn),
-                conv9=_layer(u.conv9[0], u.conv9[1]), conv11=_layer(u.conv11[0], u.conv11[1], out_perm=out_perm))
+    return dict(conv1=Conv2dSpec(u.conv1.conv, u.conv1.bn, in_perm=in_perm), conv2=Conv2dSpec(u.conv2.conv, u.conv2.bn),
+                conv3=Conv2dSpec(u.conv3.conv, u.conv3.bn), conv4=Conv2dSpec(u.conv4.conv, u.conv4.bn),
+                conv9=Conv2dSpec(u.conv9[0], u.conv9[1]), conv11=Conv2dSpec(u.conv11[0], u.conv11[1], out_perm=out_perm))
 
 
 def _block_layers(b):
-    d = dict(conv1=_layer(b.conv1, b.bn1), conv2=_layer(b.conv2, b.bn2))
+    d = dict(conv1=Conv2dSpec(b.conv1, b.bn1), conv2=Conv2dSpec(b.conv2, b.bn2))
     if b.downsample is not None:
-        d["down"] = _layer(b.downsample[0], b.downsample[1])       # downsample[1] IS bn3 (registered twice): folded once, here
+        d["down"] = Conv2dSpec(b.downsample[0], b.downsample[1])   # downsample[1] IS bn3 (registered twice): folded once, here
     return d
 
 
 def depth_net_plan(net):
-    """Every 2-D convolution of ``net`` (a ``DepthNet_Fusion`` in eval mode) as a ``_layer`` dict.  The concatenated buffer
+    """Every 2-D convolution of ``net`` (a ``DepthNet_Fusion`` in eval mode) as a ``Conv2dSpec``.  The concatenated buffer
     holds [mono_reg (128) | cost_reg (D) | zeros] -- the wide producer at column 0, the narrow one behind it, both starting
     at a multiple of 32 -- so the input channels of ``fusion_regulation.conv1`` and ``depth_reg`` and the output channels of
     ``fusion_regulation.conv11`` (whose skip is that buffer) are permuted to that order here.  ``cat_perm[new] = module index``."""
     D, f = net.depth_channels, net.fnet_mvs
     cat_perm = torch.cat([torch.arange(D, D + 128), torch.arange(D)]).to(net.depth_reg.weight.device)
-    stem = _layer(f.conv1, f.bn1)
-    # [49, 64, 3(->32)] -> [64, 160]: column (ci * 7 + kh) * 7 + kw, 147..159 zero
-    stem["w"] = F.pad(stem["w"][:, :, :3].permute(1, 2, 0).reshape(64, 147), (0, 13)).contiguous()
-    return dict(stem=stem, blocks=[_block_layers(b) for b in list(f.layer1) + list(f.layer2)], final=_layer(f.final_conv_3ddet),
-                corr=_unet_layers(net.correlation_regulation), fnet_mono=_layer(net.fnet_mono.conv, net.fnet_mono.bn),
+    stem = Conv2dSpec(f.conv1, f.bn1, pad_in=False)
+    # [49, 64, 3] -> [64, 160]: column (ci * 7 + kh) * 7 + kw, 147..159 zero
+    stem.set_weight(F.pad(stem.w.permute(1, 2, 0).reshape(64, 147), (0, 13)).contiguous())
+    return dict(stem=stem, blocks=[_block_layers(b) for b in list(f.layer1) + list(f.layer2)], final=Conv2dSpec(f.final_conv_3ddet),
+                corr=_unet_layers(net.correlation_regulation), fnet_mono=Conv2dSpec(net.fnet_mono.conv, net.fnet_mono.bn),
                 mono=_unet_layers(net.mono_regulation), fusion=_unet_layers(net.fusion_regulation, in_perm=cat_perm, out_perm=cat_perm),
-                depth_reg=_layer(net.depth_reg, in_perm=cat_perm, pad_out=False), cat_perm=cat_perm)
-
-
-def _map_plan(plan, fn):
-    if isinstance(plan, dict) and "w" in plan:
-        return fn(plan)
-    if isinstance(plan, dict):
-        return {k: _map_plan(v, fn) for k, v in plan.items()}
-    if isinstance(plan, list):
-        return [_map_plan(v, fn) for v in plan]
-    return plan
+                depth_reg=Conv2dSpec(net.depth_reg, in_perm=cat_perm, pad_out=False), cat_perm=cat_perm)
 
 
 @HEADS.register_module()
@@ -304,19 +258,6 @@ class DepthNet_Fusion(nn.Module):
         return corr / k
 
     # ---- eval mode on the GPU: every 2-D convolution on the MFMA kernels, channels-last rows --------------------------
-    def _plan(self):
-        fp = module_fingerprint(self)
-        if getattr(self, "_hip_plan", None) is not None and self._hip_plan[0] == fp:
-            return self._hip_plan[1]
-        ops = ext.ops()
-
-        def split(layer):
-            hi, lo = ops.split_operand(layer["w"])
-            return dict(layer, w=None, hi=hi, lo=lo)
-        plan = _map_plan(depth_net_plan(self), split)
-        self._hip_plan = (fp, plan)
-        return plan
-
     def _hip_ok(self, xs, imgs):
         """The shapes ``_forward_hip`` takes: images 4x the map, every stride-2 stage on an even size."""
         H, W = xs.shape[-2:]
@@ -324,76 +265,52 @@ class DepthNet_Fusion(nn.Module):
                 and H % 4 == 0 and W % 4 == 0 and xs.shape[2] % 32 == 0 and self.depth_channels % 4 == 0
                 and self.depth_channels <= 32 and xs.dtype == torch.float32 and imgs.dtype == torch.float32)
 
-    @staticmethod
-    def _conv(x, L, nhw, residual=None, relu=True, relu_after_add=False, out=None, col0=0, softmax_cols=0):
-        """One planned layer on rows ``x``; returns (rows, (N, OH, OW)).  Plain stride-1 layers go to the halo form of
-        ``sgc_conv2d_nhwc_bf16x3`` (its `relu = 2`: ReLU, then the skip), everything else to ``sgc_conv2d_nhwc_ex_bf16x3``."""
-        ops = ext.ops()
-        N, H, W = nhw
-        if L["transposed"]:
-            onhw = (N, 2 * H, 2 * W)
-        else:
-            onhw = (N, H // L["stride"], W // L["stride"])
-        if (L["stride"] == 1 and not L["transposed"] and out is None and not relu_after_add and softmax_cols == 0
-                and (residual is None or residual.shape[1] == L["hi"].shape[1])):
-            mode = (2 if residual is not None else 1) if relu else 0
-            return ops.conv2d_nhwc_bf16x3(x, L["hi"], L["lo"], nhw, L["k"], scale=L["scale"], shift=L["shift"],
-                                          residual=residual, relu=mode), onhw
-        y = ops.conv2d_nhwc_ex_bf16x3(x, L["hi"], L["lo"], nhw, L["k"], stride=L["stride"], transposed=L["transposed"],
-                                      scale=L["scale"], shift=L["shift"], residual=residual, relu=relu,
-                                      relu_after_add=relu_after_add, out=out, col0=col0, softmax_cols=softmax_cols)
-        return y, onhw
-
     def _unet(self, x, U, nhw, out=None, col0=0):
         """SimpleUnet2D on rows: conv0 + conv11(conv2 + conv9(conv4(conv3(conv2(conv1(conv0)))))); the skips ride in the epilogues
         of the transposed layers, the last of which may write a column range of a wider buffer."""
-        c1, n2 = self._conv(x, U["conv1"], nhw)
-        c2, _ = self._conv(c1, U["conv2"], n2)
-        c3, n4 = self._conv(c2, U["conv3"], n2)
-        c4, _ = self._conv(c3, U["conv4"], n4)
-        u2, _ = self._conv(c4, U["conv9"], n4, residual=c2)
-        y, _ = self._conv(u2, U["conv11"], n2, residual=x, out=out, col0=col0)
+        c1, n2 = U["conv1"](x, nhw)
+        c2, _ = U["conv2"](c1, n2)
+        c3, n4 = U["conv3"](c2, n2)
+        c4, _ = U["conv4"](c3, n4)
+        u2, _ = U["conv9"](c4, n4, residual=c2)
+        y, _ = U["conv11"](u2, n2, residual=x, out=out, col0=col0)
         return y
 
     def _fnet_mvs_hip(self, img, P):
         ops = ext.ops()
         N, _, Hi, Wi = img.shape
         st = P["stem"]
-        x = ops.conv2d_stem7_bf16x3(img.contiguous(), st["hi"], st["lo"], scale=st["scale"], shift=st["shift"], relu=True)
+        x = ops.conv2d_stem7_bf16x3(img.contiguous(), st.w_hi, st.w_lo, scale=st.scale, shift=st.shift, relu=True)
         nhw = (N, Hi // 2, Wi // 2)
         for B_ in P["blocks"]:
-            y, n1 = self._conv(x, B_["conv1"], nhw)
+            y, n1 = B_["conv1"](x, nhw)
             if "down" in B_:
-                y, _ = self._conv(y, B_["conv2"], n1)                                   # relu(bn2(conv2))
-                x, _ = self._conv(x, B_["down"], nhw, residual=y, relu=False, relu_after_add=True)   # relu(bn3(conv1x1(x)) + y)
+                y, _ = B_["conv2"](y, n1)                                               # relu(bn2(conv2))
+                x, _ = B_["down"](x, nhw, residual=y, relu=False, relu_after_add=True)  # relu(bn3(conv1x1(x)) + y)
             else:
-                x, _ = self._conv(y, B_["conv2"], n1, residual=x)                        # relu(.) + x, x >= 0: the outer ReLU is a no-op
+                x, _ = B_["conv2"](y, n1, residual=x)                                   # relu(.) + x, x >= 0: the outer ReLU is a no-op
             nhw = n1
-        f, _ = self._conv(x, P["final"], nhw, relu=False)
-        C = P["final"]["cout"]
+        f, _ = P["final"](x, nhw, relu=False)
+        C = P["final"].cout
         return f.view(nhw[0], nhw[1], nhw[2], f.shape[1])[..., :C].permute(0, 3, 1, 2)      # logical NCHW, channels-last memory
 
     def _forward_hip(self, xs, imgs, img_metas, stride):
         ops = ext.ops()
-        P = self._plan()
+        P = cached_plan(self, lambda: depth_net_plan(self))
         B, N, C, H, W = xs.shape
         D = self.depth_channels
         out = torch.empty((B, N, H, W, D), dtype=torch.float32, device=xs.device)
         nhw = (N, H, W)
-        catw = P["fusion"]["conv1"]["hi"].shape[2]
+        catw = P["fusion"]["conv1"].w.shape[2]
         for b, (x, img, img_meta) in enumerate(zip(xs, imgs, img_metas)):
             f_mvs = self._fnet_mvs_hip(img, P)
             corr = plane_sweep_correlation(f_mvs, img_meta, stride, self.depth_values, self.neighbor_img_num)
             cat = torch.empty((N * H * W, catw), dtype=torch.float32, device=xs.device)
             self._unet(ops.nchw_to_nhwc_padc(corr, 32), P["corr"], nhw, out=cat, col0=128)     # columns 128..159: cost_reg | zeros
-            if x.is_contiguous(memory_format=torch.channels_last):
-                x_rows = x.permute(0, 2, 3, 1).reshape(N * H * W, C)
-            else:
-                x_rows = ops.nchw_to_nhwc_crop(x.contiguous(), H, W).view(N * H * W, C)
-            m, _ = self._conv(x_rows, P["fnet_mono"], nhw)
+            m, _ = P["fnet_mono"](image_rows(x)[0], nhw)
             self._unet(m, P["mono"], nhw, out=cat, col0=0)                                       # columns 0..127: mono_reg
             fused = self._unet(cat, P["fusion"], nhw)
-            self._conv(fused, P["depth_reg"], nhw, relu=False, out=out[b].view(N * H * W, D), softmax_cols=D)
+            P["depth_reg"](fused, nhw, relu=False, out=out[b].view(N * H * W, D), softmax_cols=D)
         return out.permute(0, 1, 4, 2, 3)                     # [B, N, D, H, W]; every [N, D, H, W] slice channels-last in memory
 
     def forward(self, xs, imgs, img_metas, stride):

@@ -19,9 +19,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import ext
 from ..mmcv_lite import NECKS
-from .conv_plan import module_fingerprint
+from .conv_plan import Conv2dSpec, cached_plan, image_rows
 
 
 class _ConvModule(nn.Module):
@@ -75,37 +74,17 @@ class FPN(nn.Module):
         return tuple(outs)
 
     # ---- MFMA kernels on channels-last rows ----------------------------------------------------------------------
-    def _plan(self):
-        fp = module_fingerprint(self)
-        if getattr(self, "_hip_plan", None) is not None and self._hip_plan[0] == fp:
-            return self._hip_plan[1]
-        ops = ext.ops()
-
-        def spec(conv):
-            w = conv.weight.detach().float()
-            k = w.shape[2]
-            hi, lo = ops.split_operand(w.permute(2, 3, 0, 1).reshape(k * k, w.shape[0], w.shape[1]).contiguous())
-            return hi, lo, conv.bias.detach().float().contiguous(), k
-        plan = ([spec(m.conv) for m in self.lateral_convs], [spec(m.conv) for m in self.fpn_convs])
-        self._hip_plan = (fp, plan)
-        return plan
-
-    @staticmethod
-    def _rows(x):
-        """[N, C, H, W] (any strides) -> ([N*H*W, C] fp32 rows, (N, H, W)); zero-copy for channels-last memory."""
-        ops = ext.ops()
-        N, C, H, W = x.shape
-        if x.is_contiguous(memory_format=torch.channels_last) and x.dtype == torch.float32:
-            return x.permute(0, 2, 3, 1).reshape(N * H * W, C), (N, H, W)
-        return ops.nchw_to_nhwc_crop(x.float(), H, W).view(N * H * W, C), (N, H, W)
+    def _build_plan(self):
+        def spec(m):                          # bias only: no norm to fold, channel counts are multiples of 32 (``forward``)
+            return Conv2dSpec(m.conv, pad_in=False, pad_out=False, unit_scale=False)
+        return [spec(m) for m in self.lateral_convs], [spec(m) for m in self.fpn_convs]
 
     def _forward_hip(self, inputs):
-        ops = ext.ops()
-        lat_specs, out_specs = self._plan()
+        lat_specs, out_specs = cached_plan(self, self._build_plan)
         lat, dims = [], []
-        for i, (hi, lo, b, k) in enumerate(lat_specs):
-            rows, nhw = self._rows(inputs[i + self.start_level])
-            lat.append(ops.conv2d_nhwc_bf16x3(rows, hi, lo, nhw, k, shift=b))
+        for i, spec in enumerate(lat_specs):
+            rows, nhw = image_rows(inputs[i + self.start_level])
+            lat.append(spec(rows, nhw, relu=False)[0])
             dims.append(nhw)
         C = self.out_channels
         for i in range(len(lat) - 1, 0, -1):                 # top-down: nearest upsample to the finer size, add in place
@@ -114,9 +93,9 @@ class FPN(nn.Module):
             ih, iw = _nearest_index(Hd, Hs, src.device), _nearest_index(Wd, Ws, src.device)
             lat[i - 1].view(N, Hd, Wd, C).add_(src[:, ih][:, :, iw])
         outs = []
-        for i, (hi, lo, b, k) in enumerate(out_specs):
+        for i, spec in enumerate(out_specs):
             N, H, W = dims[i]
-            y = ops.conv2d_nhwc_bf16x3(lat[i], hi, lo, dims[i], k, shift=b)
+            y, _ = spec(lat[i], dims[i], relu=False)
             outs.append(y.view(N, H, W, C).permute(0, 3, 1, 2))          # logical NCHW, channels-last memory
         while len(outs) < self.num_outs:
             outs.append(outs[-1][:, :, ::2, ::2])

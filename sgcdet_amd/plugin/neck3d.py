@@ -13,8 +13,8 @@ import torch
 from torch import nn
 
 from ..mmcv_lite import NECKS
-from .conv_plan import (ConvSpec, bn_rows, conv_rows, conv_transpose_rows, module_fingerprint, rows_to_ncdhw,
-                        to_channels_last_rows, train_conv_on_hip)
+from .conv_plan import (ConvSpec, bn_rows, cached_plan, conv_rows, conv_transpose_rows, rows_to_ncdhw, to_channels_last_rows,
+                        train_conv_on_hip)
 
 
 class BasicBlock3dV2(nn.Module):
@@ -66,10 +66,7 @@ class FastIndoorImVoxelNeck(nn.Module):
             setattr(self, f"out_block_{i}", _conv_bn_relu(width, out_channels))
 
     # ---- eval-mode lowering onto the MFMA implicit-GEMM kernel ---------------------------
-    def _plan(self):
-        fp = module_fingerprint(self)
-        if getattr(self, "_hip_plan", None) is not None and self._hip_plan[0] == fp:
-            return self._hip_plan[1]
+    def _build_plan(self):
         plan = {}
         for i in range(self.n_scales):
             blocks = []
@@ -86,14 +83,13 @@ class FastIndoorImVoxelNeck(nn.Module):
                                    ConvSpec(up[3].weight, up[4], ksize=3))
             ob = getattr(self, f"out_block_{i}")
             plan[f"out_{i}"] = ConvSpec(ob[0].weight, ob[1], ksize=3)
-        self._hip_plan = (fp, plan)
         return plan
 
     def _forward_hip(self, x, tail_masks=None):
         """``tail_masks`` = (mask for up_block_1's 3x3x3, mask for out_block_0), uint8 [X*Y*Z] of the finest grid: the only
         layers whose outputs feed nothing but the finest head scale (x1 also feeds the next ConvTranspose, so every coarser
         layer stays dense).  Live rows are bit-identical to the dense launch."""
-        plan = self._plan()
+        plan = cached_plan(self, self._build_plan)
         rows, grid = to_channels_last_rows(x)
         skips = []
         for i in range(self.n_scales):

@@ -45,7 +45,7 @@ from ..mmcv_lite import (ATTENTION, TRANSFORMER, TRANSFORMER_LAYER, TRANSFORMER_
                          build_transformer_layer_sequence, constant_init, xavier_init)
 from ..functions import MultiScale3DDeformableAttnFunction_fp32
 from .. import ext
-from .conv_plan import BlockDiagSpec, LinearSpec, module_fingerprint
+from .conv_plan import BlockDiagSpec, LinearSpec, cached_plan, module_fingerprint
 
 
 def _ops():
@@ -296,9 +296,9 @@ class DeformCrossAttention_DFA3D(BaseModule):
         attention over the visible voxels); rebuilt when a parameter changes.  One kernel for all of them keeps a
         row's result independent of how many rows the call has, so the host-synchronised path and the
         device-count path (``static_counts``) are bit-identical."""
-        fp = module_fingerprint(self)
-        if self.__dict__.get("_gemm_cache") is not None and self._gemm_cache[0] == fp:
-            return self._gemm_cache[1]
+        return cached_plan(self, self._build_gemm_plan, "_gemm_cache")
+
+    def _build_gemm_plan(self):
         da, mha, C = self.deformable_attention, self.attention_pooling, self.embed_dims
         raw_w = torch.cat([da.sampling_offsets.weight, da.sampling_offsets_depth.weight, da.attention_weights.weight], 0)
         raw_b = torch.cat([da.sampling_offsets.bias, da.sampling_offsets_depth.bias, da.attention_weights.bias], 0)
@@ -321,7 +321,6 @@ class DeformCrossAttention_DFA3D(BaseModule):
                           + mha.in_proj_bias[:C].detach().float()),
             o=LinearSpec(mha.out_proj.weight, mha.out_proj.bias))
         plan.update(self._projected_query_plan(mha, plan))
-        self.__dict__["_gemm_cache"] = (fp, plan)
         return plan
 
     # Projected-query form of the inter-view attention (sgc_view_attend_pq, round 5): K and V leave the pair list.
@@ -785,9 +784,8 @@ class VoxFormerLayer(MyCustomBaseTransformerLayer):
             return _layer_norm(n2, _ffn_forward(ffn, x, None))
         ctx, row_of = got
         ops = _ops()
-        fp = (module_fingerprint(att), module_fingerprint(ffn))
-        plan = self.__dict__.get("_tail_plan")
-        if plan is None or plan[0] != fp:                       # weights split to bf16 hi / lo and fragment-packed once
+
+        def build():                                            # weights split to bf16 hi / lo and fragment-packed once
             def packed(weight):
                 hi, lo = ops.split_operand(weight.detach().float())
                 return ops.pack_b_fragments(hi), ops.pack_b_fragments(lo)
@@ -795,10 +793,9 @@ class VoxFormerLayer(MyCustomBaseTransformerLayer):
             lin1, lin2 = ffn.layers[0][0], ffn.layers[1]
             zeros = lambda n: torch.zeros(n, dtype=torch.float32, device=ctx.device)      # noqa: E731
             bias = lambda lin, n: lin.bias.detach().float().contiguous() if lin.bias is not None else zeros(n)   # noqa: E731
-            plan = (fp, packed(mha.out_proj.weight), bias(mha.out_proj, C), packed(lin1.weight), bias(lin1, lin1.out_features),
+            return (packed(mha.out_proj.weight), bias(mha.out_proj, C), packed(lin1.weight), bias(lin1, lin1.out_features),
                     packed(lin2.weight), bias(lin2, C))
-            self.__dict__["_tail_plan"] = plan
-        _, wo, bo, w1, b1, w2, b2 = plan
+        wo, bo, w1, b1, w2, b2 = cached_plan(self, build, "_tail_plan", (module_fingerprint(att), module_fingerprint(ffn)))
         y = ops.level_tail(ctx, row_of, wo, bo, (n1.weight, n1.bias, n1.eps), w1, b1, w2, b2, (n2.weight, n2.bias, n2.eps))
         return y.view(1, -1, C)
 
@@ -908,13 +905,8 @@ def _ffn_forward(ffn, x, identity=None):
                 return ffn.dropout_layer(out)
             return (x if identity is None else identity) + ffn.dropout_layer(out)
         return ffn(x, identity)
-    fp = module_fingerprint(ffn)
-    plan = ffn.__dict__.get("_sgc_plan")
-    if plan is None or plan[0] != fp:
-        lin2 = ffn.layers[1]
-        plan = (fp, LinearSpec(lin1.weight, lin1.bias), LinearSpec(lin2.weight, lin2.bias))
-        ffn.__dict__["_sgc_plan"] = plan
-    _, s1, s2 = plan
+    lin2 = ffn.layers[1]
+    s1, s2 = cached_plan(ffn, lambda: (LinearSpec(lin1.weight, lin1.bias), LinearSpec(lin2.weight, lin2.bias)), "_sgc_plan")
     ops = _ops()
     rows = x.reshape(-1, ffn.embed_dims).contiguous()
     idn = rows if identity is None else identity.reshape(-1, ffn.embed_dims).contiguous()

@@ -11,15 +11,15 @@ from golden_util import load, img_meta, max_err, fill_by_name
 
 def _apply(x, L, residual=None, relu=True, relu_after_add=False):
     """One planned layer on an NCHW tensor whose channel count is the layer's PADDED input width."""
-    k = L["k"]
-    taps, coutp, cinp = L["w"].shape
+    k = L.k
+    taps, coutp, cinp = L.w.shape
     assert x.shape[1] == cinp
-    w = L["w"].reshape(k, k, coutp, cinp)
-    if L["transposed"]:
+    w = L.w.reshape(k, k, coutp, cinp)
+    if L.transposed:
         y = F.conv_transpose2d(x, w.permute(3, 2, 0, 1), stride=2, padding=1, output_padding=1)
     else:
-        y = F.conv2d(x, w.permute(2, 3, 0, 1), stride=L["stride"], padding=k // 2)
-    y = y * L["scale"].view(1, -1, 1, 1) + L["shift"].view(1, -1, 1, 1)
+        y = F.conv2d(x, w.permute(2, 3, 0, 1), stride=L.stride, padding=k // 2)
+    y = y * L.scale.view(1, -1, 1, 1) + L.shift.view(1, -1, 1, 1)
     if relu:
         y = F.relu(y)
     if residual is not None:
@@ -58,9 +58,9 @@ def test_plan_applied_with_torch_convolutions_reproduces_the_eval_forward():
         img, xs = d["imgs"][0], d["xs"][0]
         # stem: [64, 160] rows (ci*7 + kh)*7 + kw
         st = P["stem"]
-        assert st["w"].shape == (64, 160) and st["w"][:, 147:].abs().max() == 0
-        x = F.conv2d(img, st["w"][:, :147].reshape(64, 3, 7, 7), stride=2, padding=3)
-        x = F.relu(x * st["scale"].view(1, -1, 1, 1) + st["shift"].view(1, -1, 1, 1))
+        assert st.w.shape == (64, 160) and st.w[:, 147:].abs().max() == 0
+        x = F.conv2d(img, st.w[:, :147].reshape(64, 3, 7, 7), stride=2, padding=3)
+        x = F.relu(x * st.scale.view(1, -1, 1, 1) + st.shift.view(1, -1, 1, 1))
         for B in P["blocks"]:
             y = _apply(x, B["conv1"])
             if "down" in B:
@@ -75,7 +75,7 @@ def test_plan_applied_with_torch_convolutions_reproduces_the_eval_forward():
         assert cost[:, D:].abs().max() == 0                          # padded columns stay exactly 0
         mono = _unet(_apply(xs, P["fnet_mono"]), P["mono"])
         cat = torch.cat([mono, cost], 1)                              # the buffer's column order: mono | cost | zeros
-        assert cat.shape[1] == P["fusion"]["conv1"]["w"].shape[2]
+        assert cat.shape[1] == P["fusion"]["conv1"].w.shape[2]
         fused = _unet(cat, P["fusion"])
         assert fused[:, 128 + D:].abs().max() == 0
         got = F.softmax(_apply(fused, P["depth_reg"], relu=False), dim=1)
@@ -84,13 +84,14 @@ def test_plan_applied_with_torch_convolutions_reproduces_the_eval_forward():
 
 
 def test_plan_pads_both_channel_dimensions_and_folds_the_shared_batchnorm_once():
+    from sgcdet_amd.plugin.conv_plan import Conv2dSpec
     from sgcdet_amd.plugin.depth_net import depth_net_plan
     net, d, _ = _build()
     P = depth_net_plan(net)
     D = net.depth_channels
 
     def layers(p):
-        if isinstance(p, dict) and "w" in p:
+        if isinstance(p, Conv2dSpec):
             yield p
         elif isinstance(p, dict):
             for v in p.values():
@@ -100,19 +101,19 @@ def test_plan_pads_both_channel_dimensions_and_folds_the_shared_batchnorm_once()
                 yield from layers(v)
     n = 0
     for L in layers({k: v for k, v in P.items() if k not in ("stem", "depth_reg")}):
-        taps, coutp, cinp = L["w"].shape
-        assert coutp % 32 == 0 and cinp % 32 == 0 and coutp >= L["cout"] and cinp >= L["cin"]
-        assert L["w"][:, L["cout"]:].abs().sum() == 0 and L["w"][:, :, L["cin"]:].abs().sum() == 0
-        assert (L["shift"][L["cout"]:] == 0).all() and (L["scale"][L["cout"]:] == 1).all()
+        taps, coutp, cinp = L.w.shape
+        assert coutp % 32 == 0 and cinp % 32 == 0 and coutp >= L.cout and cinp >= L.cin
+        assert L.w[:, L.cout:].abs().sum() == 0 and L.w[:, :, L.cin:].abs().sum() == 0
+        assert (L.shift[L.cout:] == 0).all() and (L.scale[L.cout:] == 1).all()
         n += 1
     assert n == 8 + 1 + 1 + 1 + 18                                   # BasicBlock convs, projection, final 1x1, fnet_mono, 3 U-Nets
-    assert P["fusion"]["conv1"]["w"].shape[2] == 160 and P["fusion"]["conv3"]["w"].shape[1:] == (576, 288)
-    assert P["depth_reg"]["w"].shape == (9, D, 160)
+    assert P["fusion"]["conv1"].w.shape[2] == 160 and P["fusion"]["conv3"].w.shape[1:] == (576, 288)
+    assert P["depth_reg"].w.shape == (9, D, 160)
     blk = net.fnet_mvs.layer2[0]
     assert blk.downsample[1] is blk.bn3                              # one BatchNorm under two keys ...
     down = P["blocks"][2]["down"]
     want = blk.bn3.weight / torch.sqrt(blk.bn3.running_var + blk.bn3.eps)
-    assert torch.allclose(down["scale"], want.detach())              # ... folded once: scale is gamma / sigma, not its square
+    assert torch.allclose(down.scale, want.detach())                 # ... folded once: scale is gamma / sigma, not its square
     # the permuted concatenation: new column j < 128 is module channel D + j (mono_reg), 128 + i is channel i (cost_reg)
     w_mod = net.depth_reg.weight.detach()
-    assert torch.equal(P["depth_reg"]["w"][4, :, :128], w_mod[:, D:, 1, 1]) and torch.equal(P["depth_reg"]["w"][4, :, 128:128 + D], w_mod[:, :D, 1, 1])
+    assert torch.equal(P["depth_reg"].w[4, :, :128], w_mod[:, D:, 1, 1]) and torch.equal(P["depth_reg"].w[4, :, 128:128 + D], w_mod[:, :D, 1, 1])
