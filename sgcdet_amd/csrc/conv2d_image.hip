@@ -5,9 +5,11 @@
 // 3x3 stride 2 up with additive skips), :241-250 (concatenation, depth_reg, softmax).  sgc_conv2d_nhwc_bf16x3 covers the stride-1
 // layers; this file adds what it does not:
 //
-//   conv2d_ex_kernel   the implicit-GEMM tile kernel of conv3d_igemm.hip restated for images: 128 rows x BN columns x 32 (K) per
-//                      256-thread workgroup, A gathered per tap from the channels-last input (buffer loads, zero rows outside the
-//                      image), bf16x3 operands split while staged into LDS, double buffered, epilogue through LDS as 16-byte rows.
+//   conv2d_ex_kernel   the implicit-GEMM tile kernel for images, on the tile core it shares with conv3d_igemm_bf16x3_kernel
+//                      (igemm_tile.hpp: LDS plan, staging deal, loads / split / stores of a K step, the MFMA loop, the C scatter and
+//                      the float4 epilogue arithmetic).  This file supplies the two policies: ADDRESSING -- GEMM row -> (image, h, w),
+//                      per tap the input pixel of every A chunk (a pixel outside the image is an out-of-range offset: zeros) and the
+//                      weight slab -- and the STORE -- row pitch, column offset, output parity, softmax.
 //                      Geometry: k in {1, 3}, stride in {1, 2}, padding k/2; or the transposed 3x3 stride-2 form (padding 1,
 //                      output_padding 1) by OUTPUT PARITY CLASS: output (2h + ph, 2w + pw) sums the taps whose parity matches --
 //                      1, 2, 2 and 4 of the 9 -- so no MFMA multiplies an inserted zero.  blockIdx.z is the class.
@@ -18,8 +20,7 @@
 //                      pixels and the whole weight matrix sit in LDS, the A fragments are gathered from the patch.
 //   nchw_pad_rows_kernel  [N, C, H, W] -> rows [N*H*W, Cp] with zero tail columns (the 12-channel cost volume enters the 32-wide rows).
 #include "common.hpp"
-#include "conv_common.hpp"
-#include "mma.hpp"
+#include "igemm_tile.hpp"
 #include "../../include/sgcdet_amd_image.h"
 
 namespace sgc {
@@ -40,221 +41,85 @@ struct Conv2dExParams {
 
 template <int BN, int NP>
 __global__ __launch_bounds__(256) void conv2d_ex_kernel(const Conv2dExParams p) {
-  constexpr int NT = 256, BMT = 128;
-  constexpr int WN = BN == 128 ? 2 : 1, WM = 4 / WN;
-  constexpr int TM = BMT / WM / 32, TN = BN / WN / 32;
-  constexpr int ACH = BMT * 8 / NT, AROWS = NT / 8;          // 4 float4 chunks of A per thread
-  constexpr int BCH = (BN * 4 + NT - 1) / NT;                // 16-byte weight chunks per thread per plane
+  using Tile = IgemmTile<BN, (BN == 128 ? 2 : 4), (BN == 128 ? 2 : 1), NP>;
+  constexpr int NT = Tile::NT, ACH = Tile::ACH;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_b[];
-  constexpr int A_PLANE = BMT * LDKH, B_PLANE = BN * LDKH, BUF = 2 * A_PLANE + 2 * B_PLANE;
-  __bf16 *base = reinterpret_cast<__bf16 *>(smem_b);
-
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int wm = wid / WN, wn = wid % WN;
-  const int m0 = blockIdx.x * BMT, n0 = blockIdx.y * BN;
+  Tile t(smem_b, threadIdx.x);
+  const int tid = t.tid;
+  const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
   const int ph = p.transposed ? (int)(blockIdx.z >> 1) : 0, pw = p.transposed ? (int)(blockIdx.z & 1) : 0;
   const int ntaps = p.transposed ? (ph + 1) * (pw + 1) : p.ksize * p.ksize;
   const int ksteps_c = p.Cin / BK;
-  const int nsteps = ntaps * ksteps_c;
 
-  // staging rows dealt as in conv3d_igemm_bf16x3_kernel (rows {r, r+4, r+8, r+12} per LDS write pass: all 64 banks)
-  const int c4 = tid & 7, rs8 = (tid >> 3) & 7;
-  const int r0 = 16 * (wid >> 1) + 2 * (wid & 1) + (rs8 >> 2) + 4 * (rs8 & 3);
-  const int bc = tid & 3, rs16 = (tid >> 2) & 15;
-  const int br0 = 16 * wid + (rs16 >> 2) + 4 * (rs16 & 3);
-  constexpr unsigned OOB = 0xfffffff0u;
+  // --- addressing: GEMM row -> (image, h, w); tap -> input pixel and weight slab ---
   int an[ACH], ah_[ACH], aw_[ACH];
   bool arow_ok[ACH];
 #pragma unroll
   for (int i = 0; i < ACH; ++i) {
-    const int m = m0 + r0 + AROWS * i;
+    const int m = m0 + t.a_row(i);
     arow_ok[i] = m < p.M;
     const int mm = arow_ok[i] ? m : 0;
     aw_[i] = mm % p.gw;
     ah_[i] = (mm / p.gw) % p.gh;
     an[i] = mm / (p.gw * p.gh);
   }
-  const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float *>(p.x), 0, (int)(unsigned)((int64_t)(p.M / (p.gh * p.gw)) * p.H * p.W * p.Cin * 4), 0x00020000);
-  const int w_bytes = (int)(unsigned)((int64_t)p.ksize * p.ksize * p.Cout * p.Cin * 2);
-  const __amdgpu_buffer_rsrc_t whr = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16 *>(p.w_hi), 0, w_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t wlr = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16 *>(p.w_lo), 0, w_bytes, 0x00020000);
-  unsigned boff[BCH];
-#pragma unroll
-  for (int i = 0; i < BCH; ++i) {
-    const int rl = br0 + 64 * i, n = n0 + rl;
-    boff[i] = (rl < BN && n < p.Cout) ? (unsigned)(n * p.Cin + bc * 8) * 2u : OOB;
-  }
-  unsigned aoff[ACH];
+  t.bind(p.x, (int64_t)(p.M / (p.gh * p.gw)) * p.H * p.W * p.Cin * 4, p.w_hi, p.w_lo, (int64_t)p.ksize * p.ksize * p.Cout * p.Cin * 2,
+         n0, p.Cout, p.Cin);
   int wtap = 0;                                   // the weight slab of the tap being loaded
-  auto set_tap = [&](int t) {
+  auto set_tap = [&](int tap) {
     int dh, dw;
     if (p.transposed) {
       // output row 2 h + ph receives input row ih through kernel row kh = 2 (h - ih) + ph + 1: ph = 0 -> (kh 1, ih h);
       // ph = 1 -> (kh 2, ih h), (kh 0, ih h + 1).  Same along the columns.
-      const int nw = pw + 1, th = t / nw, tw = t - th * nw;
+      const int nw = pw + 1, th = tap / nw, tw = tap - th * nw;
       const int kh = ph ? (th ? 0 : 2) : 1, kw = pw ? (tw ? 0 : 2) : 1;
       dh = th; dw = tw;
       wtap = kh * 3 + kw;
     } else {
-      dh = t / p.ksize - p.pad; dw = t % p.ksize - p.pad;
-      wtap = t;
+      dh = tap / p.ksize - p.pad; dw = tap % p.ksize - p.pad;
+      wtap = tap;
     }
 #pragma unroll
     for (int i = 0; i < ACH; ++i) {
       const int hh = ah_[i] * p.stride + dh, ww = aw_[i] * p.stride + dw;
       const bool ok = arow_ok[i] && hh >= 0 && hh < p.H && ww >= 0 && ww < p.W;
-      aoff[i] = ok ? ((unsigned)((an[i] * p.H + hh) * p.W + ww) * (unsigned)p.Cin + c4 * 4) * 4u : OOB;
+      t.aoff[i] = ok ? ((unsigned)((an[i] * p.H + hh) * p.W + ww) * (unsigned)p.Cin + t.c4 * 4) * 4u : Tile::OOB;
     }
   };
-  float4 ra[ACH];
-  uint4 rbh[BCH], rbl[BCH];
   int ld_tap = 0, ld_kc = 0;
   set_tap(0);
-  auto load_step = [&]() {
-    const int soff_a = __builtin_amdgcn_readfirstlane(ld_kc * (BK * 4));
-    const int soff_b = __builtin_amdgcn_readfirstlane((wtap * p.Cout * p.Cin + ld_kc * BK) * 2);
-#pragma unroll
-    for (int i = 0; i < ACH; ++i) {
-      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(xr, aoff[i], soff_a, 0);
-      ra[i] = make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
-    }
-#pragma unroll
-    for (int i = 0; i < BCH; ++i) {
-      const u32x4 h = __builtin_amdgcn_raw_buffer_load_b128(whr, boff[i], soff_b, 0);
-      rbh[i] = make_uint4(h[0], h[1], h[2], h[3]);
-      if constexpr (NP == 3) {
-        const u32x4 l = __builtin_amdgcn_raw_buffer_load_b128(wlr, boff[i], soff_b, 0);
-        rbl[i] = make_uint4(l[0], l[1], l[2], l[3]);
-      } else {
-        rbl[i] = make_uint4(0, 0, 0, 0);
-      }
-    }
+  t.run(ntaps * ksteps_c, [&]() {
+    t.load(__builtin_amdgcn_readfirstlane(ld_kc * (BK * 4)),
+           __builtin_amdgcn_readfirstlane((wtap * p.Cout * p.Cin + ld_kc * BK) * 2));
     if (++ld_kc == ksteps_c) {
       ld_kc = 0;
       if (++ld_tap < ntaps) set_tap(ld_tap);
     }
-  };
-  auto store_step = [&](int buf) {
-    __bf16 *a_hi = base + buf * BUF, *a_lo = a_hi + A_PLANE, *b_hi = a_lo + A_PLANE, *b_lo = b_hi + B_PLANE;
-#pragma unroll
-    for (int i = 0; i < ACH; ++i) {
-      const float v[4] = {ra[i].x, ra[i].y, ra[i].z, ra[i].w};
-      bf16x4 h, l;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const __bf16 hb = op_hi<NP>(v[e]);
-        h[e] = hb;
-        l[e] = op_lo<NP>(v[e], hb);
-      }
-      const int o = (r0 + AROWS * i) * LDKH + c4 * 4;
-      *reinterpret_cast<bf16x4 *>(a_hi + o) = h;
-      if constexpr (NP == 3) *reinterpret_cast<bf16x4 *>(a_lo + o) = l;
-    }
-#pragma unroll
-    for (int i = 0; i < BCH; ++i) {
-      const int rl = br0 + 64 * i;
-      if (rl >= BN) continue;
-      const int o = rl * LDKH + bc * 8;
-      *reinterpret_cast<uint4 *>(b_hi + o) = rbh[i];
-      if constexpr (NP == 3) *reinterpret_cast<uint4 *>(b_lo + o) = rbl[i];
-    }
-  };
+  });
 
-  f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int k = 0; k < 16; ++k) acc[i][j][k] = 0.f;
-
-  load_step();
-  store_step(0);
-  __syncthreads();
-  const int fr = lane & 31, fh = lane >> 5;
-  for (int s = 0; s < nsteps; ++s) {
-    const int buf = s & 1;
-    if (s + 1 < nsteps) load_step();
-    const __bf16 *a_hi = base + buf * BUF + (wm * (BMT / WM) + fr) * LDKH + fh * 8;
-    const __bf16 *a_lo = a_hi + A_PLANE;
-    const __bf16 *b_hi = base + buf * BUF + 2 * A_PLANE + (wn * (BN / WN) + fr) * LDKH + fh * 8;
-    const __bf16 *b_lo = b_hi + B_PLANE;
-#pragma unroll
-    for (int kk = 0; kk < BK / 16; ++kk) {
-      bf16x8 ah[TM], al[TM], bh[TN], bl[TN];
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        ah[i] = *reinterpret_cast<const bf16x8 *>(a_hi + i * 32 * LDKH + kk * 16);
-        if constexpr (NP == 3) al[i] = *reinterpret_cast<const bf16x8 *>(a_lo + i * 32 * LDKH + kk * 16);
-      }
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        bh[j] = *reinterpret_cast<const bf16x8 *>(b_hi + j * 32 * LDKH + kk * 16);
-        if constexpr (NP == 3) bl[j] = *reinterpret_cast<const bf16x8 *>(b_lo + j * 32 * LDKH + kk * 16);
-      }
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          if constexpr (NP == 3) {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-          }
-          acc[i][j] = mma_hh<NP>(ah[i], bh[j], acc[i][j]);
-        }
-    }
-    if (s + 1 < nsteps) store_step(buf ^ 1);
-    __syncthreads();
-  }
-
-  // epilogue through LDS (the staging buffers are free after the last barrier): 16-byte row-contiguous stores
-  constexpr int LDC = BN + 8;
-  float *cs = reinterpret_cast<float *>(smem_b);           // [BMT][LDC] <= 2 * BUF * 2 bytes for every BN
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int k = 0; k < 16; ++k)
-        cs[(wm * (BMT / WM) + i * 32 + (k & 3) + 8 * (k >> 2) + 4 * (lane >> 5)) * LDC + wn * (BN / WN) + j * 32 + (lane & 31)] =
-            acc[i][j][k];
-  __syncthreads();
+  // --- store policy: row pitch ldy, column offset col0, output parity of the transposed form, optional row softmax ---
+  float *cs = t.scatter();
   auto out_row = [&](int m) -> int64_t {
     if (!p.transposed) return m;
     const int w = m % p.gw, h = (m / p.gw) % p.gh, n = m / (p.gw * p.gh);
     return ((int64_t)n * p.OH + (2 * h + ph)) * p.OW + (2 * w + pw);
   };
-  constexpr int C4 = BN / 4;
+  constexpr int C4 = Tile::C4, LDC = Tile::LDC;
   const bool sm = p.softmax_cols > 0;
-  for (int e = tid; e < BMT * C4; e += NT) {
+  for (int e = tid; e < BM * C4; e += NT) {
     const int rl = e / C4, q = e - rl * C4;
     const int m = m0 + rl, col = n0 + q * 4;
     if (m >= p.M || col >= p.Cout) continue;
     const int64_t orow = out_row(m);
-    float4 v = *reinterpret_cast<const float4 *>(cs + rl * LDC + q * 4);
-    if (p.scale) {
-      const float4 sc4 = *reinterpret_cast<const float4 *>(p.scale + col);
-      v.x *= sc4.x; v.y *= sc4.y; v.z *= sc4.z; v.w *= sc4.w;
-    }
-    if (p.shift) {
-      const float4 sh4 = *reinterpret_cast<const float4 *>(p.shift + col);
-      v.x += sh4.x; v.y += sh4.y; v.z += sh4.z; v.w += sh4.w;
-    }
-    if (p.relu1) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-    if (p.residual) {
-      const float4 r4 = *reinterpret_cast<const float4 *>(p.residual + orow * p.ldr + col);
-      v.x += r4.x; v.y += r4.y; v.z += r4.z; v.w += r4.w;
-    }
-    if (p.relu2) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-    if (sm) *reinterpret_cast<float4 *>(cs + rl * LDC + q * 4) = v;          // (one column tile: the host checks Cout <= BN)
+    const float4 v = epilogue4(*Tile::c_quad(cs, rl, q), col, p.scale, p.shift, p.relu1, p.residual, orow * p.ldr + col, p.relu2);
+    if (sm) *Tile::c_quad(cs, rl, q) = v;                                      // (one column tile: the host checks Cout <= BN)
     else *reinterpret_cast<float4 *>(p.y + orow * p.ldy + p.col0 + col) = v;
   }
   if (!sm) return;
   __syncthreads();
   // row softmax over columns [0, softmax_cols); the columns behind them leave as they are.  One thread per row: the rows are
   // at most BN floats and this is the 12-channel depth_reg layer.
-  for (int rl = tid; rl < BMT; rl += NT) {
+  for (int rl = tid; rl < BM; rl += NT) {
     const int m = m0 + rl;
     if (m >= p.M) continue;
     float *row = cs + rl * LDC;
@@ -272,7 +137,7 @@ __global__ __launch_bounds__(256) void conv2d_ex_kernel(const Conv2dExParams p) 
 template <int BN, int NP>
 static void launch_ex_bn(const Conv2dExParams &p, dim3 grid, hipStream_t st) {
   static std::atomic<uint64_t> done{0};
-  const int smem = 2 * (2 * 128 + 2 * BN) * LDKH * 2;
+  constexpr int smem = igemm_tile_lds_bytes(BN);
   ensure_dynamic_lds((const void *)conv2d_ex_kernel<BN, NP>, smem, done);
   hipLaunchKernelGGL((conv2d_ex_kernel<BN, NP>), grid, dim3(256), smem, st, p);
 }
@@ -390,13 +255,8 @@ __global__ __launch_bounds__(256) void conv2d_stem7_kernel(const StemParams p) {
           al[e] = op_lo<NP>(v, hb);
         }
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          if constexpr (NP == 3) {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[j], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[j], acc[i][j], 0, 0, 0);
-          }
-          acc[i][j] = mma_hh<NP>(ah, bh[j], acc[i][j]);
-        }
+        for (int j = 0; j < 2; ++j)
+          acc[i][j] = mma_split<NP>(ah, al, bh[j], bl[j], acc[i][j]);
       }
     }
     // C layout: column = lane & 31, row (= pixel of the strip) = (k & 3) + 8 (k >> 2) + 4 (lane >> 5): a wave store covers
@@ -477,9 +337,7 @@ extern "C" int sgc_conv2d_nhwc_ex_bf16x3(const float *x, const uint16_t *w_hi, c
   const int bn = softmax_cols > 0 ? (Cout <= 32 ? 32 : Cout <= 64 ? 64 : 128) : ex_tile_cols(Cout);
   const dim3 grid(ceil_div(p.M, 128), ceil_div(Cout, bn), p.transposed ? 4 : 1);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (g_conv_products == 1) launch_ex<1>(p, bn, grid, st);
-  else if (g_conv_products == 2) launch_ex<2>(p, bn, grid, st);
-  else launch_ex<3>(p, bn, grid, st);
+  with_products(g_conv_products, [&](auto np) { launch_ex<np()>(p, bn, grid, st); });
   return check_launch("conv2d_ex_kernel");
 }
 
@@ -500,9 +358,7 @@ extern "C" int sgc_conv2d_stem7_bf16x3(const float *img, const uint16_t *w_hi, c
   p.ntiles = (int)ntiles; p.relu = relu ? 1 : 0;
   const int grid = (int)(ntiles < 4 * device_cus() ? ntiles : 4 * device_cus());
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (g_conv_products == 1) hipLaunchKernelGGL((conv2d_stem7_kernel<1>), dim3(grid), dim3(256), 0, st, p);
-  else if (g_conv_products == 2) hipLaunchKernelGGL((conv2d_stem7_kernel<2>), dim3(grid), dim3(256), 0, st, p);
-  else hipLaunchKernelGGL((conv2d_stem7_kernel<3>), dim3(grid), dim3(256), 0, st, p);
+  with_products(g_conv_products, [&](auto np) { hipLaunchKernelGGL((conv2d_stem7_kernel<np()>), dim3(grid), dim3(256), 0, st, p); });
   return check_launch("conv2d_stem7_kernel");
 }
 

@@ -393,7 +393,7 @@ static int conv3d_bf16x3(const float *x, const uint16_t *w_hi, const uint16_t *w
   if (rc) return rc;
   if (pl.family == kConvTile) {
     const dim3 grid(ceil_div(p.M, BM), ceil_div(Cout, pl.bn), (transposed ? 8 : 1) * p.splitk);
-    const size_t smem = (size_t)2 * (2 * BM + 2 * pl.bn) * LDKH * sizeof(uint16_t);
+    const size_t smem = igemm_tile_lds_bytes(pl.bn);
     p.xcd_deal = (p.taps > 1 || transposed) && !p.two_d ? g_tune_igemm_xcd : 0;
     launch_igemm(p, pl.bn == 64, grid, smem, st);
     rc = check_launch("conv3d_igemm_bf16x3_kernel");
@@ -549,7 +549,7 @@ static int linear_rows(const float *x, const uint16_t *w_hi, const uint16_t *w_l
   const bool narrow = Cout <= 64;
   const int bn = narrow ? 64 : 128;
   const dim3 grid(ceil_div(rows_cap, BM), ceil_div(Cout, bn), 1);
-  const size_t smem = (size_t)2 * (2 * BM + 2 * bn) * LDKH * sizeof(uint16_t);
+  const size_t smem = igemm_tile_lds_bytes(bn);
   hipStream_t st = (hipStream_t)stream;
   if (!igemm_fits_32bit(p)) return set_error(SGC_EUNSUP, "sgc_linear_rows_bf16x3: the input must stay below 4 GiB and the weights below 2 GiB");
   launch_igemm(p, narrow, grid, smem, st);

@@ -316,13 +316,7 @@ __global__ __launch_bounds__(512) void conv3d_halo_bf16x3_kernel(const ConvParam
 #pragma unroll
     for (int i = 0; i < RT; ++i)
 #pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        if constexpr (NP == 3) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.al[i], f.bh[j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.ah[i], f.bl[j], acc[i][j], 0, 0, 0);
-        }
-        acc[i][j] = mma_hh<NP>(f.ah[i], f.bh[j], acc[i][j]);
-      }
+      for (int j = 0; j < TN; ++j) acc[i][j] = mma_split<NP>(f.ah[i], f.al[i], f.bh[j], f.bl[j], acc[i][j]);
   };
   const int steps_total = (c_hi - c_lo) * NTAP;
   auto step_tap = [&](int st) { return st % NTAP; };
@@ -535,9 +529,10 @@ static int launch_halo_k(ConvParamsB &p, hipStream_t st) {
 
 template <int BX, int BY, int BZ, int BNV = 128, bool TD = false, bool WZ = false>
 static int launch_halo(ConvParamsB &p, hipStream_t st) {
-  if (g_conv_products == 1) return launch_halo_k<BX, BY, BZ, BNV, 1, TD, true, WZ>(p, st);
-  if (g_conv_products == 2) return launch_halo_k<BX, BY, BZ, BNV, 2, TD, true, WZ>(p, st);
-  if constexpr (WZ) return launch_halo_k<BX, BY, BZ, BNV, 3, TD, true, true>(p, st);
+  // the one-product modes and the Winograd stack: the software-pipelined form only.  (sgc_set_conv_products admits 1, 2 and 3 and
+  // nothing else: any other value would select the pipelined NP = 3 form here, where the old ladder fell through to the lines below.)
+  if (g_conv_products != 3 || WZ)
+    return with_products(g_conv_products, [&](auto np) { return launch_halo_k<BX, BY, BZ, BNV, np(), TD, true, WZ>(p, st); });
   // the lockstep form is kept for the fp32-faithful mode only: it is the reference of the schedule's bit-identity test, and the
   // form of the whole-grid bricks (four row tiles per wave: the unrolled pipelined loop spills 600 registers there)
   if (!g_tune_halo_stagger || BX * BY * BZ > 256) return launch_halo_k<BX, BY, BZ, BNV, 3, TD, false>(p, st);

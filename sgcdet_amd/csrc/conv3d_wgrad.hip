@@ -155,11 +155,7 @@ __global__ __launch_bounds__(WM * 128) void conv3d_wgrad_bf16x3_kernel(const Wgr
 #pragma unroll
         for (int i = 0; i < TMW; ++i)
 #pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-          }
+          for (int j = 0; j < 2; ++j) acc[i][j] = mma_split<3>(ah[i], al[i], bh[j], bl[j], acc[i][j]);
       }
       if (s + 1 < s_hi) store_step(buf ^ 1);
       __syncthreads();
@@ -373,11 +369,7 @@ __global__ __launch_bounds__(64 * NW) void conv3d_wgrad_halo_kernel(const WgradH
           }
         } else if (t < TPW - 1 || has_last) {
 #pragma unroll
-          for (int m = 0; m < MT; ++m) {
-            acc[t][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[0][m], bh[0], acc[t][m], 0, 0, 0);
-            acc[t][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[0][m], bl[0], acc[t][m], 0, 0, 0);
-            acc[t][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[0][m], bh[0], acc[t][m], 0, 0, 0);
-          }
+          for (int m = 0; m < MT; ++m) acc[t][m] = mma_split<3>(ah[0][m], al[0][m], bh[0], bl[0], acc[t][m]);
         }
       }
     }
@@ -579,7 +571,8 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_halo2_kernel(const WgradHalo
             for (int m = 0; m < MT; ++m) asm volatile("" ::"v"(ah[s & 1][m]), "v"(al[s & 1][m]));
           }
         } else if (t < TPW - 1 || has_last) {
-          // product-major: consecutive MFMAs go to different accumulators (the group fences below keep this order)
+          // product-major: consecutive MFMAs go to different accumulators (the group fences below keep this order) -- not mma_split,
+          // which would put a tile's three products back to back on one chain
 #pragma unroll
           for (int m = 0; m < MT; ++m) acc[t][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[s & 1][m], bh[n % 3], acc[t][m], 0, 0, 0);
 #pragma unroll

@@ -67,6 +67,8 @@ constexpr int BM = 128, BK = 32, LDK = BK + 4;
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 constexpr int LDKH = BK + 8;   // bf16 elements per LDS row (80 B): conflict-free ds_read_b128
+// dynamic LDS of a bf16x3 tile workgroup (igemm_tile.hpp): two buffers of A_hi | A_lo [BM][LDKH] and B_hi | B_lo [bn][LDKH]
+constexpr int igemm_tile_lds_bytes(int bn) { return 2 * (2 * BM + 2 * bn) * LDKH * 2; }
 
 struct ConvParamsB : ConvParams {
   const __bf16 *w_hi, *w_lo;   // [taps][Cout][Cin]

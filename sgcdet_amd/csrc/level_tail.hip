@@ -17,7 +17,7 @@
 //   * LayerNorm is the arithmetic of layer_norm_rows_kernel (common.hpp: ln_row_stats / ln_apply), one wave per row.
 // Every product, sum order and epilogue expression is that of the unfused kernels, so the fused level is
 // BIT-IDENTICAL to the six launches (tests/test_gpu_kernels.py checks it) -- it is a scheduling change, not a numerical one.
-#include "common.hpp"
+#include "conv_common.hpp"
 #include "mma.hpp"
 
 namespace sgc {
@@ -100,11 +100,7 @@ __global__ __launch_bounds__(C * 2, 2) void level_tail_kernel(const LevelTailPar
         ah[(kk + PD) % (PD + 1)] = *reinterpret_cast<const bf16x8 *>(a_hi + (kk + PD) * 16);
         if constexpr (NP == 3) al[(kk + PD) % (PD + 1)] = *reinterpret_cast<const bf16x8 *>(a_lo + (kk + PD) * 16);
       }
-      if constexpr (NP == 3) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[kk % (PD + 1)], bh[kk], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[kk % (PD + 1)], bl[kk], acc, 0, 0, 0);
-      }
-      acc = mma_hh<NP>(ah[kk % (PD + 1)], bh[kk], acc);
+      acc = mma_split<NP>(ah[kk % (PD + 1)], al[kk % (PD + 1)], bh[kk], bl[kk], acc);
       __builtin_amdgcn_sched_barrier(0);
     }
   };
@@ -242,8 +238,6 @@ __global__ __launch_bounds__(C * 2, 2) void level_tail_kernel(const LevelTailPar
   }
 }
 
-extern int g_conv_products;      // conv3d.hip
-
 template <int C, int NP>
 static int launch_level_tail(const LevelTailParams &p, hipStream_t st) {
   constexpr int smem = 2 * LT_ROWS * (C + 8) * 2 + LT_ROWS * C * 4 + 2 * LT_ROWS * (2 * C + 8) * 2 + LT_ROWS * 4;
@@ -294,9 +288,7 @@ extern "C" int sgc_level_tail(const float *ctx, const int32_t *row_of, const uin
   p.w2_hi = reinterpret_cast<const __bf16 *>(w2_hi); p.w2_lo = reinterpret_cast<const __bf16 *>(w2_lo); p.b2 = b2;
   p.ln2_g = ln2_gamma; p.ln2_b = ln2_beta; p.eps2 = eps2;
   p.out = out; p.Nq = Nq;
-  if (g_conv_products == 1)
-    return C == 256 ? launch_level_tail<256, 1>(p, (hipStream_t)stream) : launch_level_tail<128, 1>(p, (hipStream_t)stream);
-  if (g_conv_products == 2)
-    return C == 256 ? launch_level_tail<256, 2>(p, (hipStream_t)stream) : launch_level_tail<128, 2>(p, (hipStream_t)stream);
-  return C == 256 ? launch_level_tail<256, 3>(p, (hipStream_t)stream) : launch_level_tail<128, 3>(p, (hipStream_t)stream);
+  return with_products(g_conv_products, [&](auto np) {
+    return C == 256 ? launch_level_tail<256, np()>(p, (hipStream_t)stream) : launch_level_tail<128, np()>(p, (hipStream_t)stream);
+  });
 }

@@ -11,6 +11,7 @@
 // sgc_set_conv_products(3 | 1 | 2) selects the mode process-wide (include/sgcdet_amd.h).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
 
 namespace sgc {
 
@@ -42,6 +43,24 @@ __device__ __forceinline__ f32x16 mma_hh(bf16x8 a, bf16x8 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
   else
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+}
+// one multiply-add of the mode on one accumulator chain, in THIS order: lo*hi, hi*lo, hi*hi (results are pinned bit for bit).
+// The lo parts are references: the one-product modes never read them, and their callers never fill them.
+template <int NP>
+__device__ __forceinline__ f32x16 mma_split(const bf16x8 &ah, const bf16x8 &al, const bf16x8 &bh, const bf16x8 &bl, f32x16 c) {
+  if constexpr (NP == 3) {
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, c, 0, 0, 0);
+  }
+  return mma_hh<NP>(ah, bh, c);
+}
+
+// host: the process-wide mode (g_conv_products) as the compile-time NP of a launch -- f(std::integral_constant<int, NP>)
+template <class F>
+inline auto with_products(int products, F &&f) {
+  if (products == 1) return f(std::integral_constant<int, 1>{});
+  if (products == 2) return f(std::integral_constant<int, 2>{});
+  return f(std::integral_constant<int, 3>{});
 }
 
 }  // namespace sgc

@@ -10,13 +10,10 @@
 // (no workgroup barrier anywhere: a wave's LDS operations execute in order) -> MFMA fragments; the next chunk's loads are in flight
 // while this one multiplies.  Same products (lo*hi + hi*lo + hi*hi) and the same K order as the dense GEMM over the group's K range:
 // the zero blocks of the dense form add exact zeros, so the two agree bit for bit.
-#include "common.hpp"
+#include "conv_common.hpp"
 #include "mma.hpp"
 
 namespace sgc {
-
-extern int g_conv_products;
-int device_cus();
 
 struct BdParams {
   const float *x;              // [rows_cap][8 K]
@@ -98,12 +95,9 @@ __global__ __launch_bounds__(512) void rows_blockdiag_kernel(const BdParams p) {
 #pragma unroll
       for (int kk = 0; kk < BD_KC / 16; ++kk) {
         const bf16x8 ah = *reinterpret_cast<const bf16x8 *>(fa + kk * 16);
-        if constexpr (NP == 3) {
-          const bf16x8 al = *reinterpret_cast<const bf16x8 *>(fa + 32 * BD_PITCH + kk * 16);
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[ph * (BD_KC / 16) + kk], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[ph * (BD_KC / 16) + kk], acc, 0, 0, 0);
-        }
-        acc = mma_hh<NP>(ah, bh[ph * (BD_KC / 16) + kk], acc);
+        bf16x8 al = ah;                                      // read in the three-product mode only
+        if constexpr (NP == 3) al = *reinterpret_cast<const bf16x8 *>(fa + 32 * BD_PITCH + kk * 16);
+        acc = mma_split<NP>(ah, al, bh[ph * (BD_KC / 16) + kk], bl[ph * (BD_KC / 16) + kk], acc);
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
@@ -128,17 +122,11 @@ static int launch_blockdiag(const BdParams &p, hipStream_t st) {
   const size_t smem = (size_t)8 * 2 * 32 * BD_PITCH * sizeof(uint16_t);      // 136 KB: one workgroup per CU
   const int tiles = ceil_div(p.rows_cap, 32);
   const int grid = tiles < device_cus() ? tiles : device_cus();
-  static std::atomic<uint64_t> done[3] = {};
-  if (g_conv_products == 1) {
-    ensure_dynamic_lds((const void *)rows_blockdiag_kernel<K, 1>, (int)smem, done[0]);
-    hipLaunchKernelGGL((rows_blockdiag_kernel<K, 1>), dim3(grid), dim3(512), smem, st, p);
-  } else if (g_conv_products == 2) {
-    ensure_dynamic_lds((const void *)rows_blockdiag_kernel<K, 2>, (int)smem, done[1]);
-    hipLaunchKernelGGL((rows_blockdiag_kernel<K, 2>), dim3(grid), dim3(512), smem, st, p);
-  } else {
-    ensure_dynamic_lds((const void *)rows_blockdiag_kernel<K, 3>, (int)smem, done[2]);
-    hipLaunchKernelGGL((rows_blockdiag_kernel<K, 3>), dim3(grid), dim3(512), smem, st, p);
-  }
+  with_products(g_conv_products, [&](auto np) {
+    static std::atomic<uint64_t> done{0};                  // one per NP: a static of the generic lambda's instantiation
+    ensure_dynamic_lds((const void *)rows_blockdiag_kernel<K, np()>, (int)smem, done);
+    hipLaunchKernelGGL((rows_blockdiag_kernel<K, np()>), dim3(grid), dim3(512), smem, st, p);
+  });
   return check_launch("rows_blockdiag_kernel");
 }
 

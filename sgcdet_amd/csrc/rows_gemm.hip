@@ -29,7 +29,7 @@
 // The k order and the product order are those of conv3d_igemm_bf16x3_kernel: both kernels give identical bits.
 #include <stdlib.h>
 
-#include "common.hpp"
+#include "conv_common.hpp"
 #include "tuning.hpp"
 #include "mma.hpp"
 #include "diag.hpp"
@@ -223,11 +223,7 @@ __global__ __launch_bounds__(NW * 64, 2) void rows_gemm_bf16x3_kernel(const Rows
         ah[(kk + PD) % (PD + 1)] = *reinterpret_cast<const bf16x8 *>(a_hi + (kk + PD) * 16);
         if constexpr (NP == 3) al[(kk + PD) % (PD + 1)] = *reinterpret_cast<const bf16x8 *>(a_lo + (kk + PD) * 16);
       }
-      if constexpr (NP == 3) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[kk % (PD + 1)], bh[kk], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[kk % (PD + 1)], bl[kk], acc, 0, 0, 0);
-      }
-      acc = mma_hh<NP>(ah[kk % (PD + 1)], bh[kk], acc);
+      acc = mma_split<NP>(ah[kk % (PD + 1)], al[kk % (PD + 1)], bh[kk], bl[kk], acc);
       __builtin_amdgcn_sched_barrier(0);
     }
   };
@@ -402,8 +398,6 @@ __global__ __launch_bounds__(NW * 64, 2) void rows_gemm_bf16x3_kernel(const Rows
   }
 }
 
-extern int g_conv_products;      // conv3d.hip
-
 // ---------------------------------------------------------------------------------------------
 // Gather form at K = 256 (round 6): PRODUCER and CONSUMER waves.  In the kernel above a wave stages its share of the next tile AND
 // multiplies the current one: at K = 256 with the gather that is the resident weights of its 32 columns (128 registers) plus a tile in
@@ -464,11 +458,7 @@ __global__ __launch_bounds__(512) void rows_gemm_gather_pc_kernel(const RowsGemm
           ah[(kk + PD) % (PD + 1)] = *reinterpret_cast<const bf16x8 *>(a_hi + (kk + PD) * 16);
           if constexpr (NP == 3) al[(kk + PD) % (PD + 1)] = *reinterpret_cast<const bf16x8 *>(a_lo + (kk + PD) * 16);
         }
-        if constexpr (NP == 3) {
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[kk % (PD + 1)], bh[kk], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[kk % (PD + 1)], bl[kk], acc, 0, 0, 0);
-        }
-        acc = mma_hh<NP>(ah[kk % (PD + 1)], bh[kk], acc);
+        acc = mma_split<NP>(ah[kk % (PD + 1)], al[kk % (PD + 1)], bh[kk], bl[kk], acc);
         __builtin_amdgcn_sched_barrier(0);
       }
       int n4 = p.N * 4;
@@ -556,9 +546,9 @@ static int launch_rows_gemm_np(const RowsGemmParams &p, int grid, hipStream_t st
 
 template <int K, int NW, int DEPTH, int EPI>
 static int launch_rows_gemm_e(const RowsGemmParams &p, int grid, hipStream_t st) {
-  if (g_conv_products == 1) return launch_rows_gemm_np<K, NW, 1, EPI, 1>(p, grid, st);      // single-product modes: the lockstep-1 form
-  if (g_conv_products == 2) return launch_rows_gemm_np<K, NW, 1, EPI, 2>(p, grid, st);
-  return launch_rows_gemm_np<K, NW, DEPTH, EPI, 3>(p, grid, st);
+  return with_products(g_conv_products, [&](auto np) {      // single-product modes: the lockstep-1 form
+    return launch_rows_gemm_np<K, NW, np() == 3 ? DEPTH : 1, EPI, np()>(p, grid, st);
+  });
 }
 
 template <int K, int NW, int DEPTH>
@@ -611,19 +601,11 @@ static void launch_gather_pc(const RowsGemmParams &p, int grid, hipStream_t st) 
 template <int K>
 static int launch_rows_gemm_gather(const RowsGemmParams &p, int grid, hipStream_t st) {
   constexpr int smem = 2 * 2 * RG_ROWS * (K + 8) * (int)sizeof(uint16_t);
-  static std::atomic<uint64_t> attr_done{0};
-  if (g_conv_products == 1) {
-    ensure_dynamic_lds((const void *)rows_gemm_bf16x3_kernel<K, 4, 1, 0, 1, true>, smem, attr_done);
-    hipLaunchKernelGGL((rows_gemm_bf16x3_kernel<K, 4, 1, 0, 1, true>), dim3(grid), dim3(256), smem, st, p);
-  } else if (g_conv_products == 2) {
-    static std::atomic<uint64_t> attr2{0};
-    ensure_dynamic_lds((const void *)rows_gemm_bf16x3_kernel<K, 4, 1, 0, 2, true>, smem, attr2);
-    hipLaunchKernelGGL((rows_gemm_bf16x3_kernel<K, 4, 1, 0, 2, true>), dim3(grid), dim3(256), smem, st, p);
-  } else {
-    static std::atomic<uint64_t> attr3{0};
-    ensure_dynamic_lds((const void *)rows_gemm_bf16x3_kernel<K, 4, 1, 0, 3, true>, smem, attr3);
-    hipLaunchKernelGGL((rows_gemm_bf16x3_kernel<K, 4, 1, 0, 3, true>), dim3(grid), dim3(256), smem, st, p);
-  }
+  with_products(g_conv_products, [&](auto np) {
+    static std::atomic<uint64_t> attr_done{0};             // one per NP: a static of the generic lambda's instantiation
+    ensure_dynamic_lds((const void *)rows_gemm_bf16x3_kernel<K, 4, 1, 0, np(), true>, smem, attr_done);
+    hipLaunchKernelGGL((rows_gemm_bf16x3_kernel<K, 4, 1, 0, np(), true>), dim3(grid), dim3(256), smem, st, p);
+  });
   return check_launch("rows_gemm_bf16x3_kernel (gather)");
 }
 
@@ -645,9 +627,7 @@ int rows_gemm_gather_launch(const float *x, int64_t x_rows, const float *gw, con
     int s8 = device_cus();                                      // one 8-wave workgroup per CU
     if (g_tune_rows_cu_pct > 0 && g_tune_rows_cu_pct < 100) s8 = s8 * g_tune_rows_cu_pct / 100;
     if (s8 > cap_tiles) s8 = cap_tiles;
-    if (g_conv_products == 1) launch_gather_pc<1>(p, s8, st);
-    else if (g_conv_products == 2) launch_gather_pc<2>(p, s8, st);
-    else launch_gather_pc<3>(p, s8, st);
+    with_products(g_conv_products, [&](auto np) { launch_gather_pc<np()>(p, s8, st); });
     return check_launch("rows_gemm_gather_pc_kernel");
   }
   return launch_rows_gemm_gather<128>(p, grid, st);

@@ -154,6 +154,56 @@ def test_stem7_against_float64(gpu_ops, nhw):
         assert err < 1e-4 * want.abs().max().item()
 
 
+def _round_to_mode(t, mode):
+    """An fp32 operand as the one-product modes multiply it: bfloat16 (mode 1) or saturated IEEE half (mode 2)."""
+    return (t.bfloat16() if mode == 1 else t.clamp(-65504.0, 65504.0).half()).float()
+
+
+@pytest.mark.parametrize("mode", [1, 2])
+def test_one_product_modes_against_float64_of_the_rounded_operands(gpu_ops, mode):
+    """sgc_set_conv_products 1 / 2 on conv2d_ex_kernel (32- and 64-column tiles, every form, residual and both ReLUs) and on the
+    stem.  The yardstick is the float64 formulation of operands ROUNDED to the mode, so only the fp32 accumulation separates the
+    two, as in mode 3: the same 1e-4 of the output scale."""
+    ops = gpu_ops
+    try:
+        ops.lib.call("sgc_set_conv_products", mode)
+        split = ops.split_operand          # the planes of the mode just selected, as the prepared layers make them
+        nhw, Cin = (2, 6, 10), 32
+        N, H, W = nhw
+        for Cout, cout_live in [(32, 24), (160, 140)]:
+            for k, stride, transposed in FORMS:
+                g = torch.Generator().manual_seed(1000 * mode + 100 * k + 10 * stride + int(transposed) + Cout)
+                x = torch.randn(N * H * W, Cin, generator=g)
+                w = torch.randn(k * k, Cout, Cin, generator=g) / (k * Cin ** 0.5)
+                w[:, cout_live:] = 0
+                scale, shift = 0.5 + torch.rand(Cout, generator=g), 0.3 * torch.randn(Cout, generator=g)
+                OH, OW = (2 * H, 2 * W) if transposed else (H // stride, W // stride)
+                res = torch.randn(N * OH * OW, Cout, generator=g)
+                hi, lo = split(w.cuda())
+                got = ops.conv2d_nhwc_ex_bf16x3(x.cuda(), hi, lo, nhw, k, stride=stride, transposed=transposed, scale=scale.cuda(),
+                                                shift=shift.cuda(), residual=res.cuda(), relu=True, relu_after_add=True)
+                want = _ref_conv(_round_to_mode(x, mode), _round_to_mode(w, mode), nhw, k, stride, transposed, scale, shift, res, 1, 1, 0)
+                assert torch.isfinite(want).all() and got.shape == want.shape
+                err, sc = max_err(got, want), want.abs().max().item()
+                print(f"mode {mode} conv2d_ex k{k} s{stride} t{int(transposed)} Cout {Cout}: err {err:.3e} scale {sc:.3f}")
+                assert err < 1e-4 * sc
+        N, H, W = 2, 12, 20
+        g = torch.Generator().manual_seed(mode)
+        img = torch.randn(N, 3, H, W, generator=g)
+        w = torch.randn(64, 3, 7, 7, generator=g) / 147 ** 0.5
+        scale, shift = 0.5 + torch.rand(64, generator=g), 0.3 * torch.randn(64, generator=g)
+        hi, lo = split(F.pad(w.reshape(64, 147), (0, 13)).contiguous().cuda())
+        got = ops.conv2d_stem7_bf16x3(img.cuda(), hi, lo, scale=scale.cuda(), shift=shift.cuda(), relu=True)
+        want = F.conv2d(_round_to_mode(img, mode).double(), _round_to_mode(w, mode).double(), stride=2, padding=3)
+        want = (want * scale.double().view(1, -1, 1, 1) + shift.double().view(1, -1, 1, 1)).clamp_min(0).permute(0, 2, 3, 1).reshape(-1, 64)
+        assert torch.isfinite(want).all() and got.shape == want.shape
+        err, sc = max_err(got, want), want.abs().max().item()
+        print(f"mode {mode} stem7: err {err:.3e} scale {sc:.3f}")
+        assert err < 1e-4 * sc
+    finally:
+        ops.lib.call("sgc_set_conv_products", 3)
+
+
 def test_refused_shapes_and_padded_transpose(gpu_ops):
     ops = gpu_ops
     assert not ops.conv2d_nhwc_ex_supported((1, 5, 8), 32, 32, 3, stride=2)           # odd H at a stride-2 stage
