@@ -122,22 +122,22 @@ __global__ __launch_bounds__(NW * 64) void dfa3d_bwd_tile_kernel(const BwdTilePa
       const int64_t g = ((int64_t)item * p.LM + lm) * p.P + min(pt, p.P - 1);
       const float x = p.loc[g * 3], y = p.loc[g * 3 + 1], z = p.loc[g * 3 + 2];
       const float aw = p.attn ? p.attn[g] : 1.f;
-      Sample sm;
+      Sample sm;      // (LEFT OUT of the shared geometry: make_sample_unclamped, and the clamped h0 / w0 below, as they stood)
       float taps[8];                                                // the depth taps of the four corners: phase 3 needs them again
-      make_sample(sm, dcam, p.D, p.H, p.W, p.D, x, y, z, 1.f, taps);
+      make_sample_unclamped(sm, dcam, p.D, p.H, p.W, p.D, x, y, z, taps);
       const int h0 = (int)__builtin_amdgcn_fmed3f(floorf(sample_coord(y, fH)), -2.f, fH);
       const int w0 = (int)__builtin_amdgcn_fmed3f(floorf(sample_coord(x, fW)), -2.f, fW);
       // bit k: corner k (gather order (h0,w0) (h0,w1) (h1,w0) (h1,w1)) lies in the map and the sample passes the 2-D gate
       int okm = 0;
 #pragma unroll
       for (int k = 0; k < 4; ++k) okm |= (samp_live && sm.off[k] >= 0) ? (1 << k) : 0;
-      const float sgx = sm.s[0], sgy = sm.s[1], sgz = sm.s[3], sgw = sm.s[2];      // gather order
+      const float sgx = sm.sg[0], sgy = sm.sg[1], sgz = sm.sg[2], sgw = sm.sg[3];
       // ---- this lane's sample -> the queue.  Window rows ty0 = h0 - y0, ty0 + 1; pixels tx0 = w0 - x0, tx0 + 1.  A row pair is applied
       //      as TWO ADJACENT window pixels starting at bx0 = clamp(tx0, 0, tw - 2): the weights move with the clamp, a corner whose
       //      pixel is outside the window keeps weight 0 here (the row arithmetic below adds it with a global atomic) ----
       {
-        const float hh = 1.f - sm.lh, hw = 1.f - sm.lw;
-        const float ak[4] = {hh * hw * sgx * aw, hh * sm.lw * sgy * aw, sm.lh * hw * sgz * aw, sm.lh * sm.lw * sgw * aw};
+        const Bilinear bil = bilinear(sm.lh, sm.lw);
+        const float ak[4] = {bil.w[0] * sgx * aw, bil.w[1] * sgy * aw, bil.w[2] * sgz * aw, bil.w[3] * sgw * aw};
         const int tx0 = w0 - x0, ty0 = h0 - y0;
         const int bx0 = min(max(tx0, 0), p.tw - 2);
         int offs[2], own[2];
@@ -202,11 +202,8 @@ __global__ __launch_bounds__(NW * 64) void dfa3d_bwd_tile_kernel(const BwdTilePa
       };
       auto sample = [&](const int s, const float lh, const float lw, const float aws, const int sh0, const int sw0, const int som,
                         const float s0, const float s1, const float s2, const float s3) {
-        const float hh = 1.f - lh, hw = 1.f - lw;
         const float sg[4] = {s0, s1, s2, s3};
-        const float bil[4] = {hh * hw, hh * lw, lh * hw, lh * lw};
-        const float dh_c[4] = {-hw, -lw, hw, lw};                   // d(bilinear weight)/dh, /dw: wms_deform_attn_cuda_kernel.cuh:116-150
-        const float dw_c[4] = {-hh, hh, -lh, lh};
+        const Bilinear bil = bilinear(lh, lw);
         float part[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         float val[NCH][4], ghw[NCH][4], gww[NCH][4], tgv[NCH][4];
 #pragma unroll
@@ -218,7 +215,7 @@ __global__ __launch_bounds__(NW * 64) void dfa3d_bwd_tile_kernel(const BwdTilePa
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           const bool okk = (som >> k) & 1;
-          const float ak = bil[k] * sg[k];
+          const float ak = bil.w[k] * sg[k];
           const int tx = sw0 + (k & 1) - x0, ty = sh0 + (k >> 1) - y0;
           const bool inside = ((unsigned)tx < (unsigned)p.tw) & ((unsigned)ty < (unsigned)p.th);
           float gsk = 0.f;
@@ -228,9 +225,9 @@ __global__ __launch_bounds__(NW * 64) void dfa3d_bwd_tile_kernel(const BwdTilePa
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               const float v = okk ? v4[e] : 0.f;
-              ghw[j][e] += sg[k] * dh_c[k] * v;
-              gww[j][e] += sg[k] * dw_c[k] * v;
-              gsk += v * bil[k] * tgv[j][e];
+              ghw[j][e] += sg[k] * bil.dh[k] * v;
+              gww[j][e] += sg[k] * bil.dw[k] * v;
+              gsk += v * bil.w[k] * tgv[j][e];
               val[j][e] += ak * v;
             }
           }
@@ -285,6 +282,7 @@ __global__ __launch_bounds__(NW * 64) void dfa3d_bwd_tile_kernel(const BwdTilePa
           for (int k = 0; k < 4; ++k) {                             // gather order: res[3 + k] is d/dscore of corner k, taps[2k], [2k+1] its depth taps
             const int hk = h0 + (k >> 1), wk = w0 + (k & 1);
             const float gs = res[3 + k];
+            // (in-map test redone from h0, w0: sm.off held live across the row arithmetic costs the Cm = 32 form its second wave)
             if (hk >= 0 && hk <= p.H - 1 && wk >= 0 && wk <= p.W - 1 && gs != 0.f && !(p.diag & 8)) {
               const int tx = wk - x0, ty = hk - y0;
               const bool inside = ((unsigned)tx < (unsigned)p.tw) & ((unsigned)ty < (unsigned)p.th);

@@ -129,7 +129,7 @@ __global__ __launch_bounds__(256) void dfa3d_fwd_kernel(const FwdParams p) {
       if (r == 0) lds_b[il] = b;
       if (live && p.score)
         reinterpret_cast<float4 *>(p.score)[(int64_t)item * SPI + r] =
-            make_float4(sm.s[0], sm.s[1], sm.s[2], sm.s[3]);
+            ref_order(make_float4(sm.sg[0], sm.sg[1], sm.sg[2], sm.sg[3]));
     }
   }
   __syncthreads();
@@ -303,8 +303,6 @@ __global__ __launch_bounds__(256) void dfa3d_fwd_wave_kernel(const FwdParams p) 
     const char *vbytes = reinterpret_cast<const char *>(p.value);
     const unsigned rowb = ((ZR ? 0u : (unsigned)b_[il] * (unsigned)p.S * (unsigned)MC) + (unsigned)(m * Cm + c0)) * 4u;
     const unsigned rstride = (unsigned)MC * 4u;
-    const float *vbase = p.value + (int64_t)b_[il] * p.S * MC + (m * Cm + c0);
-    (void)vbase;
     const int d0 = il * SPI + m * LP;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     if (PT > 0) {
@@ -415,17 +413,15 @@ __global__ void depth_score_fwd_kernel(const float *__restrict__ dist, const int
                                        float *__restrict__ score, int64_t total, int S, int M, int D,
                                        int L, int Q, int P) {
   for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (int64_t)gridDim.x * blockDim.x) {
-    const int pt = (int)(g % P);
     const int l = (int)((g / P) % L);
     const int m = (int)((g / ((int64_t)P * L)) % M);
     const int64_t bq = g / ((int64_t)P * L * M);
     const int b = (int)(bq / Q);
-    (void)pt;
     const int H = (int)shapes3[l * 3], W = (int)shapes3[l * 3 + 1], Dl = (int)shapes3[l * 3 + 2];
     const float *dpx = dist + (((int64_t)b * S + lsi[l]) * M + m) * D;
     Sample sm;
     make_sample(sm, dpx, (int64_t)M * D, H, W, Dl, loc3[g * 3], loc3[g * 3 + 1], loc3[g * 3 + 2], 1.f);
-    reinterpret_cast<float4 *>(score)[g] = make_float4(sm.s[0], sm.s[1], sm.s[2], sm.s[3]);
+    reinterpret_cast<float4 *>(score)[g] = ref_order(make_float4(sm.sg[0], sm.sg[1], sm.sg[2], sm.sg[3]));
   }
 }
 
@@ -453,24 +449,20 @@ __global__ __launch_bounds__(256) void wms_fwd_kernel(const float *__restrict__ 
       const float *vb = value + ((int64_t)b * S + lsi[l]) * MC + m * Cm + c0;
       for (int pt = 0; pt < P; ++pt) {
         const int64_t s = (sidx * L + l) * P + pt;
-        const float h_im = sample_coord(loc2[s * 2 + 1], (float)H), w_im = sample_coord(loc2[s * 2], (float)W);
-        if (!(h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W)) continue;
-        const float hf = floorf(h_im), wf = floorf(w_im);
-        const int h0 = (int)hf, w0 = (int)wf, h1 = h0 + 1, w1 = w0 + 1;
-        const float lh = h_im - hf, lw = w_im - wf, hh = 1.f - lh, hw = 1.f - lw;
-        const float4 sc = reinterpret_cast<const float4 *>(score)[s];
+        Sample sm;
+        const Corners c = sample_2d(sm, H, W, loc2[s * 2], loc2[s * 2 + 1]);
+        if (!sm.in2) continue;
+        const Bilinear bil = bilinear(sm.lh, sm.lw);
+        const float4 sc = ref_order(reinterpret_cast<const float4 *>(score)[s]);
         const float aw = attn[s];
-        const bool ok[4] = {h0 >= 0 && w0 >= 0, h0 >= 0 && w1 <= W - 1, h1 <= H - 1 && w0 >= 0,
-                            h1 <= H - 1 && w1 <= W - 1};
-        const int px[4] = {h0 * W + w0, h0 * W + w1, h1 * W + w0, h1 * W + w1};
-        const float wk[4] = {hh * hw * sc.x, hh * lw * sc.y, lh * hw * sc.w, lh * lw * sc.z};
+        const float wk[4] = {bil.w[0] * sc.x, bil.w[1] * sc.y, bil.w[2] * sc.z, bil.w[3] * sc.w};
         float val[VEC];
 #pragma unroll
         for (int v = 0; v < VEC; ++v) val[v] = 0.f;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-          if (!ok[k]) continue;
-          const float *src = vb + (int64_t)px[k] * MC;
+          if (!c.ok[k]) continue;
+          const float *src = vb + (int64_t)c.px[k] * MC;
           if (VEC == 4) {
             const float4 x4 = *reinterpret_cast<const float4 *>(src);
             val[0] += wk[k] * x4.x; val[1 % VEC] += wk[k] * x4.y; val[2 % VEC] += wk[k] * x4.z; val[3 % VEC] += wk[k] * x4.w;
@@ -653,7 +645,7 @@ extern "C" int sgc_pairs_deform_gather(const float *value, const float *dist, co
   if (P > 64 || (P & (P - 1)))
     return set_error(SGC_EUNSUP, "sgc_pairs_deform_gather: P must be a power of two <= 64 (wave-shuffle softmax)");
   FwdParams p = {};
-  p.value = value; p.dist = dist; p.dist_pairs = dist_pairs_or_null; p.ref_cam = ref_cam; p.raw = raw;
+  p.value = value; p.dist = dist; p.dist_pairs = D >= 2 ? dist_pairs_or_null : nullptr; p.ref_cam = ref_cam; p.raw = raw;
   p.pair_cam = pair_cam; p.pair_q = pair_q;
   p.totals = totals; p.out = out;
   if (cam_stride_or_0 > 0 && cam_stride_or_0 < H * W) return set_error(SGC_EINVAL, "sgc_pairs_deform_gather: cam_stride < H*W");

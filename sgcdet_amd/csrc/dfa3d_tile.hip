@@ -44,11 +44,7 @@ namespace sgc {
 //           inside a bin is the ascending original pair index, identical from run to run), then the move.
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ int ref_bin(float u, float v, int H, int W, int bw, int bh, int nbx) {
-#pragma clang fp contract(off)
-  const float w_im = u * (float)W - 0.5f, h_im = v * (float)H - 0.5f;
-  int px = (int)floorf(w_im), py = (int)floorf(h_im);
-  px = min(max(px, 0), W - 1);
-  py = min(max(py, 0), H - 1);
+  const int px = min(max(sample_axis(u, (float)W).i0, 0), W - 1), py = min(max(sample_axis(v, (float)H).i0, 0), H - 1);
   return (py / bh) * nbx + px / bw;
 }
 
@@ -375,13 +371,12 @@ __global__ __launch_bounds__(NW * 64) void dfa3d_fwd_tile_kernel(const TileParam
         r4_n = p.raw[((int64_t)iun * p.M + m) * P + pt];
       }
 
+      // sample_geom.hpp's geometry (sample_axis, sample_corners, depth_taps: the reasons are there), WRITTEN OUT: built from the helpers,
+      // this kernel's register allocation moves (a wave per SIMD less or more instructions in 10 - 24 of its 40 forms: profiles/r12_sample_geometry.md)
       const float h_im = sample_coord(y, fH), w_im = sample_coord(x, fW), d_im = sample_coord(z, fD);
-      // bitwise & on purpose: with && the compiler evaluates the later comparisons under an exec mask (an s_and_saveexec /
-      // s_or pair per chain -- 13 of them per step); every operand here is cheap and side-effect free
       const bool in2 = (h_im > -1.f) & (w_im > -1.f) & (h_im < fH) & (w_im < fW);
       const bool in3 = in2 & (d_im > -1.f) & (d_im < fD);
       const float hf = floorf(h_im), wf = floorf(w_im), df = floorf(d_im);
-      // (int) of a huge float is undefined: clamp the floats first (in2 / in3 already hold the decision)
       const int h0 = (int)__builtin_amdgcn_fmed3f(hf, -2.f, fH), w0 = (int)__builtin_amdgcn_fmed3f(wf, -2.f, fW);
       const int d0 = (int)__builtin_amdgcn_fmed3f(df, -2.f, fD);
       const float lh = h_im - hf, lw = w_im - wf, ld = d_im - df;

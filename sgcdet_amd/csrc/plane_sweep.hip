@@ -31,7 +31,6 @@ __global__ __launch_bounds__(256) void plane_sweep_corr_kernel(const float *__re
   const int tiles = (HW + PS_PIX - 1) / PS_PIX;
   const int n = blockIdx.x / tiles, pix0 = (blockIdx.x % tiles) * PS_PIX;
   const float inv_sqrt_c = 1.0f / sqrtf((float)C);
-  const float half_w = (float)(W - 1) / 2.0f, half_h = (float)(H - 1) / 2.0f;
   for (int pp = 0; pp < PS_PIX / 4; ++pp) {
     const int pl = wid * (PS_PIX / 4) + pp;
     const int pix = pix0 + pl;
@@ -57,22 +56,9 @@ __global__ __launch_bounds__(256) void plane_sweep_corr_kernel(const float *__re
         float wgt[DG][4];
 #pragma unroll
         for (int j = 0; j < DG; ++j) {
-          const float dep = depth[min(d0 + j, D - 1)];
-          const float px = rx * dep + m[3], py = ry * dep + m[7], pz = rz * dep + m[11];   // * depth + trans
-          const float u = px / pz, v_ = py / pz;
-          const float gx = u / half_w - 1.0f, gy = v_ / half_h - 1.0f;          // the reference's normalisation
-          const float ix = ((gx + 1.0f) * (float)W - 1.0f) / 2.0f;              // grid_sample, align_corners = False
-          const float iy = ((gy + 1.0f) * (float)H - 1.0f) / 2.0f;
-          const bool in = ix > -1.0f && iy > -1.0f && ix < (float)W && iy < (float)H;   // false for NaN / inf too
-          const float x0f = in ? floorf(ix) : 0.f, y0f = in ? floorf(iy) : 0.f;
-          const int x0 = (int)x0f, y0 = (int)y0f, x1 = x0 + 1, y1 = y0 + 1;
-          const float lx = ix - x0f, ly = iy - y0f, hx = 1.0f - lx, hy = 1.0f - ly;
-          const bool okx0 = in && x0 >= 0, okx1 = in && x1 <= W - 1, oky0 = in && y0 >= 0, oky1 = in && y1 <= H - 1;
-          const int cx0 = max(x0, 0), cx1 = min(x1, W - 1), cy0 = max(y0, 0), cy1 = min(y1, H - 1);
-          off[j][0] = (cy0 * W + cx0) * C; wgt[j][0] = (oky0 && okx0) ? hx * hy : 0.f;   // nw, ne, sw, se
-          off[j][1] = (cy0 * W + cx1) * C; wgt[j][1] = (oky0 && okx1) ? lx * hy : 0.f;
-          off[j][2] = (cy1 * W + cx0) * C; wgt[j][2] = (oky1 && okx0) ? hx * ly : 0.f;
-          off[j][3] = (cy1 * W + cx1) * C; wgt[j][3] = (oky1 && okx1) ? lx * ly : 0.f;
+          const PlaneSweepCorners c = plane_sweep_corners(rx, ry, rz, m, depth[min(d0 + j, D - 1)], H, W);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) { off[j][q] = c.idx[q] * C; wgt[j][q] = c.w[q]; }
         }
         float val[DG][4][VPL];
 #pragma unroll

@@ -21,8 +21,8 @@
 // short list by its contents before summing, so grad_feat is bitwise reproducible run to run whenever no list is longer
 // than PSB_CHUNK (every row at the measured shapes).  A longer list is summed in atomic-fill order and
 // its chunks are added by float atomics: those rows differ from run to run by fp32 reordering only.
-// Which corners count follows the forward exactly (same position arithmetic, op for op): a corner off the image or a
-// non-finite position adds nothing.
+// Which corners count follows the forward exactly (both call plane_sweep_corners, sample_geom.hpp): a corner off the image
+// or a non-finite position adds nothing.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -38,34 +38,6 @@ namespace sgc {
 constexpr int PSB_MAXD = 32;
 constexpr int PSB_CHUNK = 512;           // entries per wave of a split list (Appendix B: 512-row chunks measured)
 constexpr int PSB_SCAN = 2048;           // counts per workgroup of the scan (256 threads x 8)
-
-// The forward's sample position and corner weights (plane_sweep.hip, plane_sweep_corr_kernel), op for op.
-struct PsbCorners {
-  int idx[4];       // pixel index in the neighbour view (clamped: valid to read even where ok is false)
-  float w[4];       // nw, ne, sw, se
-  bool ok[4];       // corner on the image (false for every corner of a non-finite / off-image position)
-};
-
-__device__ __forceinline__ PsbCorners psb_corners(float rx, float ry, float rz, const float *m, float dep, int H, int W) {
-  const float half_w = (float)(W - 1) / 2.0f, half_h = (float)(H - 1) / 2.0f;
-  const float px = rx * dep + m[3], py = ry * dep + m[7], pz = rz * dep + m[11];
-  const float u = px / pz, v_ = py / pz;
-  const float gx = u / half_w - 1.0f, gy = v_ / half_h - 1.0f;
-  const float ix = ((gx + 1.0f) * (float)W - 1.0f) / 2.0f;
-  const float iy = ((gy + 1.0f) * (float)H - 1.0f) / 2.0f;
-  const bool in = ix > -1.0f && iy > -1.0f && ix < (float)W && iy < (float)H;
-  const float x0f = in ? floorf(ix) : 0.f, y0f = in ? floorf(iy) : 0.f;
-  const int x0 = (int)x0f, y0 = (int)y0f, x1 = x0 + 1, y1 = y0 + 1;
-  const float lx = ix - x0f, ly = iy - y0f, hx = 1.0f - lx, hy = 1.0f - ly;
-  const bool okx0 = in && x0 >= 0, okx1 = in && x1 <= W - 1, oky0 = in && y0 >= 0, oky1 = in && y1 <= H - 1;
-  const int cx0 = max(x0, 0), cx1 = min(x1, W - 1), cy0 = max(y0, 0), cy1 = min(y1, H - 1);
-  PsbCorners r;
-  r.idx[0] = cy0 * W + cx0; r.ok[0] = oky0 && okx0; r.w[0] = r.ok[0] ? hx * hy : 0.f;
-  r.idx[1] = cy0 * W + cx1; r.ok[1] = oky0 && okx1; r.w[1] = r.ok[1] ? lx * hy : 0.f;
-  r.idx[2] = cy1 * W + cx0; r.ok[2] = oky1 && okx0; r.w[2] = r.ok[2] ? hx * ly : 0.f;
-  r.idx[3] = cy1 * W + cx1; r.ok[3] = oky1 && okx1; r.w[3] = r.ok[3] ? lx * ly : 0.f;
-  return r;
-}
 
 __global__ __launch_bounds__(256) void psb_zero_kernel(uint32_t *__restrict__ p, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = 0u;
@@ -89,7 +61,7 @@ __global__ __launch_bounds__(256) void psb_route_kernel(const int32_t *__restric
   const int64_t dst0 = (int64_t)m_view * HW;
   const int src = n * HW + p;
   for (int d = 0; d < D; ++d) {
-    const PsbCorners c = psb_corners(rx, ry, rz, m, depth[d], H, W);
+    const PlaneSweepCorners c = plane_sweep_corners(rx, ry, rz, m, depth[d], H, W);
     const float g = FILL ? grad_corr[((int64_t)n * D + d) * HW + p] : 0.f;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -282,7 +254,7 @@ __global__ __launch_bounds__(256) void psb_final_kernel(const float *__restrict_
 #pragma unroll
       for (int j = 0; j < DG; ++j) {
         const int d = min(d0 + j, D - 1);
-        const PsbCorners c = psb_corners(rx, ry, rz, m, depth[d], H, W);
+        const PlaneSweepCorners c = plane_sweep_corners(rx, ry, rz, m, depth[d], H, W);
         const float g = d0 + j < D ? __int_as_float(__builtin_amdgcn_readlane(__float_as_int(gl), d)) : 0.f;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {

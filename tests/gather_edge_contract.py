@@ -143,6 +143,13 @@ FUSED_CASES = [
     ("two-level", 2, 8, 32, 4, 4, [(8, 16), (4, 8)], False),
     ("two-level-rep", 2, 8, 32, 4, 4, [(8, 16), (4, 8)], True),
 ]
+# the split `_ext` operators (depth_score_* / wms_*) take a per-head depth distribution: dist_heads == M throughout.
+# "hot": the float4 path; "scalar": Cm % 4 != 0, one channel per lane and per atomic; "two-level": a non-zero level start
+SPLIT_CASES = [
+    ("hot", 2, 8, 32, 4, 4, [(8, 16)], True),
+    ("scalar", 2, 8, 5, 4, 4, [(8, 16)], True),
+    ("two-level", 2, 8, 32, 4, 4, [(8, 16), (4, 8)], True),
+]
 # (name, Cm, (H, W), D): N = 2 cameras, M = 8, P = 4
 PAIR_CASES = [("cm32", 32, (8, 16), 4), ("cm16", 16, (16, 8), 8)]
 GEOMETRY_CASES = [("c256", 256, (8, 16), 4), ("c128", 128, (16, 8), 8)]
@@ -331,6 +338,29 @@ def pairs_geometry_sample_ref(feat, dist, ref_cam, pair_cam, pair_q, H, W, varia
     return out.reshape(loc.shape[0], -1)
 
 
+def split_reference(c, variant=None):
+    """The fused operator's float64 results for ``fused_inputs`` -> dict(out, score [B,Q,M,L,P,4] reference corner order, grads)."""
+    d = lambda k: c[k].double()
+    out, score = dfa3d_forward_ref(d("value"), d("dist"), c["shapes3"], c["lsi"], d("loc"), d("attn"), variant)
+    _, grads = dfa3d_backward_ref(c["value"], c["dist"], c["shapes3"], c["lsi"], c["loc"], c["attn"], c["go"], variant=variant)
+    return dict(out=out, score=score, grads=grads)
+
+
+def split_operators(ops, c, to=lambda t: t):
+    """depth_score_forward -> wms_forward and wms_backward -> depth_score_backward of ``ops`` (the HIP library or the C oracle) on
+    ``fused_inputs``; ``to`` moves a tensor to the device.  grad_loc is assembled as (gl2.x, gl2.y, gl3.z)."""
+    t = {k: to(c[k]) for k in ("value", "dist", "shapes3", "lsi", "loc", "attn", "go")}
+    s2, l2 = t["shapes3"][:, :2].contiguous(), t["loc"][..., :2].contiguous()
+    score = ops.depth_score_forward(t["dist"], t["shapes3"], t["lsi"], t["loc"])
+    out = ops.wms_forward(t["value"], s2, t["lsi"], l2, t["attn"], score)
+    gv, gl2, ga, gs = (torch.zeros_like(x) for x in (t["value"], l2, t["attn"], score))
+    ops.wms_backward(t["value"], s2, t["lsi"], l2, t["attn"], score, t["go"], gv, gl2, ga, gs)
+    gd, gl3 = torch.zeros_like(t["dist"]), torch.zeros_like(t["loc"])
+    ops.depth_score_backward(t["dist"], t["shapes3"], t["lsi"], t["loc"], gs, gd, gl3)
+    return dict(out=out, score=score, grad_value=gv, grad_dist=gd, grad_loc=torch.cat([gl2, gl3[..., 2:]], -1), grad_attn=ga,
+                gl3_uv=gl3[..., :2])
+
+
 # --------------------------------------------------------------------------------------------------------------------
 # comparisons
 # --------------------------------------------------------------------------------------------------------------------
@@ -358,3 +388,13 @@ def check_rows(a, b, mag, what, tol=FWD_TOL):
     print(f"{what}: element-wise err {e:.3e} of max(1, sum |terms|) (bound {tol:.0e})")
     assert e <= tol, f"{what}: element-wise {e:.3e} > {tol:.0e}"
     return e
+
+
+def check_split(got, ref, what, log=None):
+    """``split_operators`` against ``split_reference``: forward and scores at FWD_TOL, the four gradients at BWD_TOL, and the uv
+    gradient through the score (which the reference drops) exactly 0."""
+    check(got["out"], ref["out"], FWD_TOL, f"{what} forward", log)
+    check(got["score"], ref["score"], FWD_TOL, f"{what} score", log)
+    for name, want in zip(("grad_value", "grad_dist", "grad_loc", "grad_attn"), ref["grads"]):
+        check(got[name], want, BWD_TOL, f"{what} {name}", log)
+    assert not got["gl3_uv"].any(), f"{what}: gl3.x / gl3.y must be exactly 0"

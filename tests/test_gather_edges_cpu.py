@@ -82,6 +82,44 @@ def test_reference_matches_oracle_pairs_geometry_sample(case, interior, oracle_o
     check_rows(got, want, mag, "oracle pairs_geometry_sample")
 
 
+@pytest.fixture(scope="module")
+def split(oracle_ops):
+    """case name -> (inputs, the oracle's split operators on them): computed once, shared by the comparison and the teeth."""
+    cache = {}
+
+    def get(name):
+        if name not in cache:
+            c = gc.fused_inputs(next(c for c in gc.SPLIT_CASES if c[0] == name))
+            cache[name] = (c, gc.split_operators(oracle_ops, c))
+        return cache[name]
+    return get
+
+
+@pytest.mark.parametrize("name", [c[0] for c in gc.SPLIT_CASES])
+def test_reference_matches_oracle_split_operators(name, split):
+    """Largest error over the three cases: 1.2e-07 of the scale forward (score 6.0e-08), 2.6e-07 backward (grad_loc, two-level)."""
+    c, got = split(name)
+    for l, (h, w) in enumerate(c["levels"]):
+        gc.assert_coverage(gc.t_im_of(c["loc"][:, :, :, l], h, w, c["D"]), h, w, c["D"], f"split {name} level {l}")
+    gc.check_split(got, gc.split_reference(c), f"oracle split {name}")
+
+
+@pytest.mark.parametrize("variant", gc.VARIANTS)
+def test_wrong_sampling_rules_fail_the_split_comparison(variant, split):
+    """The split path's own results against the reference under each wrong rule: more than 100 bounds away, where
+    test_wrong_sampling_rules_miss_the_reference_by_100_bounds says the rule can show (the inclusive gate: grad_loc only)."""
+    for case in gc.SPLIT_CASES:
+        c, got = split(case[0])
+        ref = gc.split_reference(c, variant)
+        fwd = gc.rel_err(got["out"], ref["out"])
+        bwd = {n: gc.rel_err(got[n], w) for n, w in zip(GRADS, ref["grads"])}
+        print(f"{variant} / split {case[0]}: forward {fwd:.3e}, backward {max(bwd.values()):.3e} of the scale")
+        if variant == "inclusive":
+            assert fwd <= FWD_TOL and bwd["grad_loc"] > 100 * FWD_TOL
+        else:
+            assert fwd > 100 * FWD_TOL and max(bwd.values()) > 100 * FWD_TOL
+
+
 def test_every_gpu_tensor_covers_every_gate_class():
     for case in gc.FUSED_CASES:
         c = gc.fused_inputs(case)
@@ -89,6 +127,10 @@ def test_every_gpu_tensor_covers_every_gate_class():
             t = gc.t_im_of(c["loc"][:, :, :, l], h, w, c["D"])             # from the fp32 tensor the kernels read
             counts, combo = gc.assert_coverage(t, h, w, c["D"], f"fused {case[0]} level {l}")
             print(case[0], l, "rarest class", min(counts.values()), "rarest corner pair", combo)
+    for case in gc.SPLIT_CASES:
+        c = gc.fused_inputs(case)
+        for l, (h, w) in enumerate(c["levels"]):
+            gc.assert_coverage(gc.t_im_of(c["loc"][:, :, :, l], h, w, c["D"]), h, w, c["D"], f"split {case[0]} level {l}")
     for _, Cm, HW, D in gc.PAIR_CASES:
         p = gc.pair_inputs(Cm, HW, D)
         gc.assert_coverage(gc.t_im_of(p["loc"], *HW, D), *HW, D, f"pairs Cm {Cm}")

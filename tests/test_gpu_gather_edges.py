@@ -93,6 +93,27 @@ def test_item_list_operator_and_backward(name, fused, gpu_ops):
         check(x, y, BWD_TOL, f"items {name} {gname}")
 
 
+# ---- the four split `_ext` operators: depth_score_forward -> wms_forward, wms_backward -> depth_score_backward -----------
+@pytest.fixture(scope="module")
+def split():
+    cache = {}
+
+    def get(name):
+        if name not in cache:
+            c = gc.fused_inputs(next(c for c in gc.SPLIT_CASES if c[0] == name))
+            cache[name] = (c, gc.split_reference(c))
+        return cache[name]
+    return get
+
+
+@pytest.mark.parametrize("name", [c[0] for c in gc.SPLIT_CASES])
+def test_split_ext_operators_and_backward(name, split, gpu_ops):
+    c, ref = split(name)
+    for l, (h, w) in enumerate(c["levels"]):
+        gc.assert_coverage(gc.t_im_of(c["loc"][:, :, :, l], h, w, c["D"]), h, w, c["D"], f"split {name} level {l}")
+    gc.check_split(gc.split_operators(gpu_ops, c, cu), ref, f"split {name}")
+
+
 # ---- the pair-list gather: both kernels, 1 / 2 / 4 samples per lane, three sources of the depth taps -------------------
 @pytest.mark.parametrize("variant", [0, 1])
 @pytest.mark.parametrize("name", [c[0] for c in gc.PAIR_CASES])
