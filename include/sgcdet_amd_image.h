@@ -1,6 +1,6 @@
 /*
- * sgcdet_amd_image.h -- image-side 2-D convolutions of the MI355X (gfx950) library: what DepthNet_Fusion's CNNs need beyond
- * sgc_conv2d_nhwc_bf16x3 (csrc/conv2d_image.hip).
+ * sgcdet_amd_image.h -- image-side 2-D convolutions of the MI355X (gfx950) library: what DepthNet_Fusion's CNNs and the ResNet
+ * backbone need beyond sgc_conv2d_nhwc_bf16x3 (csrc/conv2d_image.hip, csrc/maxpool2d.hip).
  *
  * The calls declared here have no twin in the CPU oracle (oracle/sgc_oracle.c mirrors include/sgcdet_amd.h only); their
  * checkers are torch's F.conv2d / F.conv_transpose2d in float64 and the reference class's own output
@@ -42,6 +42,23 @@ int sgc_conv2d_nhwc_ex_bf16x3(const float *x, const uint16_t *w_hi, const uint16
                               int softmax_cols, sgc_stream_t stream);
 int sgc_conv2d_nhwc_ex_supported(int N, int H, int W, int Cin, int Cout, int ksize, int stride, int transposed, int ldy,
                                  int col0, int ldr /* 0: no residual */, int softmax_cols);
+
+/* The same kernel, arguments, epilogue and restrictions as sgc_conv2d_nhwc_ex_bf16x3 (transposed must be 0), for stride-2 layers
+ * over maps of ANY size: OH = (H + 1) / 2, OW = (W + 1) / 2 at stride 2 -- nn.Conv2d with padding ksize / 2 for ksize 1 and 3 (the
+ * ResNet stages: 15 x 20 -> 8 x 10).  y and residual have N*OH*OW rows.  On sizes both entries accept the results are
+ * bit-identical; sgc_conv2d_nhwc_ex_bf16x3 and its _supported twin keep refusing odd sizes. */
+int sgc_conv2d_nhwc_strided_bf16x3(const float *x, const uint16_t *w_hi, const uint16_t *w_lo, const float *scale,
+                                   const float *shift, const float *residual_or_null, float *y, int N, int H, int W, int Cin,
+                                   int Cout, int ksize, int stride, int transposed, int flags, int ldy, int col0, int ldr,
+                                   int softmax_cols, sgc_stream_t stream);
+int sgc_conv2d_nhwc_strided_supported(int N, int H, int W, int Cin, int Cout, int ksize, int stride, int transposed, int ldy,
+                                      int col0, int ldr /* 0: no residual */, int softmax_cols);
+
+/* nn.MaxPool2d(kernel_size=3, stride=2, padding=1) over channels-last rows (the pooling behind the ResNet stem):
+ *   x [N*H*W, C] -> y [N*OH*OW, C], OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1, any H, W >= 1.
+ * Padding takes no part in the maximum (a window always holds its centre pixel, so no -inf is stored); NaN propagates.
+ * Needs C % 4 == 0 and 16-byte aligned pointers (SGC_EUNSUP otherwise). */
+int sgc_maxpool2d_nhwc(const float *x, float *y, int N, int H, int W, int C, sgc_stream_t stream);
 
 /* The ResNet stem: 7x7 stride-2 padding-3 convolution of fp32 NCHW images img [N, 3, H, W] to 64 channels,
  * v = acc * scale + shift (folded BatchNorm and bias), optional ReLU, written as channels-last rows y [N*(H/2)*(W/2), 64].

@@ -120,12 +120,15 @@ TRAIN_INTROSPECTION = {
 # include/sgcdet_amd_image.h: the 2-D convolutions of the image-side CNNs (no CPU-oracle twin)
 IMAGE_SIGNATURES = {
     "sgc_conv2d_nhwc_ex_bf16x3": [_p] * 7 + [_i] * 13 + [_p],
+    "sgc_conv2d_nhwc_strided_bf16x3": [_p] * 7 + [_i] * 13 + [_p],
+    "sgc_maxpool2d_nhwc": [_p, _p] + [_i] * 4 + [_p],
     "sgc_conv2d_stem7_bf16x3": [_p] * 6 + [_i] * 4 + [_p],
     "sgc_nchw_to_nhwc_padc": [_p, _p] + [_i] * 5 + [_p],
 }
 
 IMAGE_INTROSPECTION = {
     "sgc_conv2d_nhwc_ex_supported": (C.c_int, [_i] * 12),
+    "sgc_conv2d_nhwc_strided_supported": (C.c_int, [_i] * 12),
 }
 
 CONV2D_RELU, CONV2D_RELU_AFTER_ADD = 1, 2      # SGC_CONV2D_* flags of include/sgcdet_amd_image.h

@@ -15,6 +15,8 @@
 //                      1, 2, 2 and 4 of the 9 -- so no MFMA multiplies an inserted zero.  blockIdx.z is the class.
 //                      Epilogue: v = acc * scale + shift; relu; + residual (own row pitch); relu; store at row pitch ldy, column
 //                      offset col0 (two producers fill one concatenated buffer); optional softmax over the first columns.
+//                      Two entries launch it: sgc_conv2d_nhwc_ex_bf16x3 (stride 2 on even sizes only) and
+//                      sgc_conv2d_nhwc_strided_bf16x3 (stride 2 on any size: the ResNet stages on odd maps).
 //   conv2d_stem7_kernel  7x7 stride-2 padding-3 convolution of fp32 NCHW images with 3 channels to 64 channels, folded BatchNorm +
 //                      ReLU, channels-last rows out.  K = 3 * 49 = 147 padded to 160; the image patch of a tile of 8 x 32 output
 //                      pixels and the whole weight matrix sit in LDS, the A fragments are gathered from the patch.
@@ -155,21 +157,23 @@ static int ex_tile_cols(int Cout) {
   return c128 <= c64 ? 128 : 64;
 }
 
+// `any_size`: the strided entry (sgc_conv2d_nhwc_strided_bf16x3) -- a stride-2 layer over any H, W, output ceil(H / 2) x ceil(W / 2)
 static const char *ex_unsupported(int N, int H, int W, int Cin, int Cout, int ksize, int stride, int transposed, int ldy, int col0,
-                                  int ldr, int softmax_cols, bool has_residual) {
+                                  int ldr, int softmax_cols, bool has_residual, bool any_size = false) {
   if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return "non-positive size";
   if (Cin % 32 || Cout % 4) return "needs Cin % 32 == 0 and Cout % 4 == 0";
   if (transposed) {
+    if (any_size) return "the any-size strided entry has no transposed form";
     if (ksize != 3 || stride != 2) return "the transposed form is 3x3 stride 2 (padding 1, output_padding 1)";
   } else {
     if ((ksize != 1 && ksize != 3) || (stride != 1 && stride != 2)) return "ksize in {1, 3}, stride in {1, 2}";
-    if (stride == 2 && ((H | W) & 1)) return "a stride-2 layer needs even H and W";
+    if (stride == 2 && ((H | W) & 1) && !any_size) return "a stride-2 layer needs even H and W";
   }
   if (ldy % 4 || col0 % 4 || col0 < 0 || col0 + Cout > ldy) return "needs ldy % 4 == 0, col0 % 4 == 0 and col0 + Cout <= ldy";
   if (has_residual && (ldr % 4 || ldr < Cout)) return "needs ldr % 4 == 0 and ldr >= Cout";
   if (softmax_cols < 0 || softmax_cols > Cout || (softmax_cols > 0 && Cout > 128)) return "softmax needs softmax_cols <= Cout <= 128";
   const int s = transposed ? 1 : stride;
-  const int64_t OH = transposed ? 2 * H : H / s, OW = transposed ? 2 * W : W / s;
+  const int64_t OH = transposed ? 2 * H : (H + s - 1) / s, OW = transposed ? 2 * W : (W + s - 1) / s;    // == H / s on the sizes !any_size accepts
   if ((int64_t)N * H * W * Cin * 4 >= (int64_t)0xfffffff0u || (int64_t)ksize * ksize * Cout * Cin * 2 >= ((int64_t)1 << 31) ||
       (int64_t)N * OH * OW >= ((int64_t)1 << 31) || (int64_t)N * H * W >= ((int64_t)1 << 31))
     return "tensor too large for 32-bit buffer offsets";
@@ -308,20 +312,23 @@ extern "C" int sgc_conv2d_nhwc_ex_supported(int N, int H, int W, int Cin, int Co
   return ex_unsupported(N, H, W, Cin, Cout, ksize, stride, transposed, ldy, col0, ldr, softmax_cols, ldr > 0) ? 0 : 1;
 }
 
-extern "C" int sgc_conv2d_nhwc_ex_bf16x3(const float *x, const uint16_t *w_hi, const uint16_t *w_lo, const float *scale,
-                                         const float *shift, const float *residual_or_null, float *y, int N, int H, int W,
-                                         int Cin, int Cout, int ksize, int stride, int transposed, int flags, int ldy, int col0,
-                                         int ldr, int softmax_cols, sgc_stream_t stream) {
-  if (!x || !w_hi || !w_lo || !y) return set_error(SGC_EINVAL, "sgc_conv2d_nhwc_ex_bf16x3: null pointer");
-  if (flags & ~(SGC_CONV2D_RELU | SGC_CONV2D_RELU_AFTER_ADD)) return set_error(SGC_EINVAL, "sgc_conv2d_nhwc_ex_bf16x3: unknown flag");
+// The two entries of conv2d_ex_kernel.  Only the host side tells them apart: `any_size` admits odd H, W at stride 2, where the output
+// is ceil(H / 2) x ceil(W / 2) (nn.Conv2d with padding k / 2).  The kernel walks M = N * OH * OW GEMM rows and bounds-checks every
+// input pixel it addresses (row 2 oh + 1 of a 3x3 window on the last row of an odd image reads as zeros, like the padding), so on
+// sizes both entries accept they launch the same kernel with the same parameters.
+static int conv2d_ex(const char *who, bool any_size, const float *x, const uint16_t *w_hi, const uint16_t *w_lo, const float *scale,
+                     const float *shift, const float *residual_or_null, float *y, int N, int H, int W, int Cin, int Cout, int ksize,
+                     int stride, int transposed, int flags, int ldy, int col0, int ldr, int softmax_cols, sgc_stream_t stream) {
+  if (!x || !w_hi || !w_lo || !y) return set_error(SGC_EINVAL, "%s: null pointer", who);
+  if (flags & ~(SGC_CONV2D_RELU | SGC_CONV2D_RELU_AFTER_ADD)) return set_error(SGC_EINVAL, "%s: unknown flag", who);
   // every tensor moves as 16-byte vectors (buffer loads of x and the weight planes, float4 of scale / shift / residual / y)
   if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w_hi) | reinterpret_cast<uintptr_t>(w_lo) |
        reinterpret_cast<uintptr_t>(scale) | reinterpret_cast<uintptr_t>(shift) | reinterpret_cast<uintptr_t>(residual_or_null) |
        reinterpret_cast<uintptr_t>(y)) & 15)
-    return set_error(SGC_EUNSUP, "sgc_conv2d_nhwc_ex_bf16x3: pointers must be 16-byte aligned");
+    return set_error(SGC_EUNSUP, "%s: pointers must be 16-byte aligned", who);
   if (const char *why = ex_unsupported(N, H, W, Cin, Cout, ksize, stride, transposed, ldy, col0, ldr, softmax_cols,
-                                       residual_or_null != nullptr))
-    return set_error(SGC_EUNSUP, "sgc_conv2d_nhwc_ex_bf16x3: %s", why);
+                                       residual_or_null != nullptr, any_size))
+    return set_error(SGC_EUNSUP, "%s: %s", who, why);
   Conv2dExParams p = {};
   p.x = x; p.w_hi = reinterpret_cast<const __bf16 *>(w_hi); p.w_lo = reinterpret_cast<const __bf16 *>(w_lo);
   p.scale = scale; p.shift = shift; p.residual = residual_or_null; p.y = y;
@@ -329,7 +336,7 @@ extern "C" int sgc_conv2d_nhwc_ex_bf16x3(const float *x, const uint16_t *w_hi, c
   p.ksize = ksize; p.transposed = transposed ? 1 : 0;
   p.stride = p.transposed ? 1 : stride;
   p.pad = p.transposed ? 0 : ksize / 2;
-  p.OH = p.transposed ? 2 * H : H / stride; p.OW = p.transposed ? 2 * W : W / stride;
+  p.OH = p.transposed ? 2 * H : (H + stride - 1) / stride; p.OW = p.transposed ? 2 * W : (W + stride - 1) / stride;
   p.gh = p.transposed ? H : p.OH; p.gw = p.transposed ? W : p.OW;
   p.M = N * p.gh * p.gw;
   p.relu1 = (flags & SGC_CONV2D_RELU) ? 1 : 0; p.relu2 = (flags & SGC_CONV2D_RELU_AFTER_ADD) ? 1 : 0;
@@ -339,6 +346,27 @@ extern "C" int sgc_conv2d_nhwc_ex_bf16x3(const float *x, const uint16_t *w_hi, c
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   with_products(g_conv_products, [&](auto np) { launch_ex<np()>(p, bn, grid, st); });
   return check_launch("conv2d_ex_kernel");
+}
+
+extern "C" int sgc_conv2d_nhwc_ex_bf16x3(const float *x, const uint16_t *w_hi, const uint16_t *w_lo, const float *scale,
+                                         const float *shift, const float *residual_or_null, float *y, int N, int H, int W,
+                                         int Cin, int Cout, int ksize, int stride, int transposed, int flags, int ldy, int col0,
+                                         int ldr, int softmax_cols, sgc_stream_t stream) {
+  return conv2d_ex("sgc_conv2d_nhwc_ex_bf16x3", false, x, w_hi, w_lo, scale, shift, residual_or_null, y, N, H, W, Cin, Cout, ksize,
+                   stride, transposed, flags, ldy, col0, ldr, softmax_cols, stream);
+}
+
+extern "C" int sgc_conv2d_nhwc_strided_supported(int N, int H, int W, int Cin, int Cout, int ksize, int stride, int transposed,
+                                                 int ldy, int col0, int ldr, int softmax_cols) {
+  return ex_unsupported(N, H, W, Cin, Cout, ksize, stride, transposed, ldy, col0, ldr, softmax_cols, ldr > 0, true) ? 0 : 1;
+}
+
+extern "C" int sgc_conv2d_nhwc_strided_bf16x3(const float *x, const uint16_t *w_hi, const uint16_t *w_lo, const float *scale,
+                                              const float *shift, const float *residual_or_null, float *y, int N, int H, int W,
+                                              int Cin, int Cout, int ksize, int stride, int transposed, int flags, int ldy, int col0,
+                                              int ldr, int softmax_cols, sgc_stream_t stream) {
+  return conv2d_ex("sgc_conv2d_nhwc_strided_bf16x3", true, x, w_hi, w_lo, scale, shift, residual_or_null, y, N, H, W, Cin, Cout, ksize,
+                   stride, transposed, flags, ldy, col0, ldr, softmax_cols, stream);
 }
 
 extern "C" int sgc_conv2d_stem7_bf16x3(const float *img, const uint16_t *w_hi, const uint16_t *w_lo, const float *scale,

@@ -76,6 +76,7 @@ def build_from_cfg(cfg, registry, default_args=None):
 
 # registries named as the reference names them (mmdet.models / mmcv.cnn.bricks.registry)
 DETECTORS = Registry("detector")
+BACKBONES = Registry("backbone")
 HEADS = Registry("head")
 NECKS = Registry("neck")
 LOSSES = Registry("loss")
@@ -84,6 +85,10 @@ FEEDFORWARD_NETWORK = Registry("feed-forward network")
 TRANSFORMER_LAYER = Registry("transformerLayer")
 TRANSFORMER_LAYER_SEQUENCE = Registry("transformer-layers sequence")
 TRANSFORMER = Registry("Transformer")
+
+
+def build_backbone(cfg):
+    return BACKBONES.build(cfg)
 
 
 def build_head(cfg):

@@ -11,11 +11,12 @@ from .bbox_head import ImVoxelHeadV2, ScanNetImVoxelHeadV2, SunRgbdImVoxelHeadV2
 from .detector import SGCDet
 from .depth_net import DepthNet_Fusion, ResNetFPN, SimpleUnet2D, ConvBnReLU2D
 from .fpn import FPN
+from .resnet import ResNet
 
 __all__ = [
     "MSDeformableAttention3D_DFA3D", "DeformCrossAttention_DFA3D", "MyCustomBaseTransformerLayer",
     "VoxFormerLayer", "VoxFormerEncoder_DFA3D", "PerceptionTransformer_DFA3D", "compute_projection",
     "AdaptiveSparseHead", "DenseHead", "topk_wo_grad", "FastIndoorImVoxelNeck", "BasicBlock3dV2",
     "ImVoxelHeadV2", "ScanNetImVoxelHeadV2", "SunRgbdImVoxelHeadV2", "get_points", "SGCDet",
-    "DepthNet_Fusion", "ResNetFPN", "SimpleUnet2D", "ConvBnReLU2D", "FPN",
+    "DepthNet_Fusion", "ResNetFPN", "SimpleUnet2D", "ConvBnReLU2D", "FPN", "ResNet",
 ]

@@ -1,7 +1,7 @@
 """What the eval-mode lowerings of the plugin modules share: a module's layers prepared once for the library's kernels.
 
-``ConvSpec`` (3-D: neck and head, ``sgc_conv3d_cl_*`` / Winograd-z), ``Conv2dSpec`` (2-D: FPN and depth net,
-``sgc_conv2d_nhwc_bf16x3`` / ``sgc_conv2d_nhwc_ex_bf16x3``), ``LinearSpec`` and ``BlockDiagSpec`` (the row GEMMs of the
+``ConvSpec`` (3-D: neck and head, ``sgc_conv3d_cl_*`` / Winograd-z), ``Conv2dSpec`` (2-D: backbone, FPN and depth net,
+``sgc_conv2d_nhwc_bf16x3`` / ``sgc_conv2d_nhwc_ex_bf16x3`` / ``sgc_conv2d_nhwc_strided_bf16x3``), ``LinearSpec`` and ``BlockDiagSpec`` (the row GEMMs of the
 transformer) each hold one layer as the kernels take it and dispatch it in ``__call__``.  Eval BatchNorm (running statistics)
 and the bias are folded into a per-channel scale / shift for the kernel's epilogue (``fold_norm``, the only copy), weights are
 permuted once to ``[tap][Cout][Cin]``, and channel counts are zero-padded to multiples of 32 (the K tile; ``_pad_to``) with zero
@@ -173,10 +173,18 @@ class Conv2dSpec:
 
     def __call__(self, x, nhw, residual=None, relu=True, relu_after_add=False, out=None, col0=0, softmax_cols=0):
         """The layer on rows ``x``; returns (rows, (N, OH, OW)).  Plain stride-1 layers go to the halo form of
-        ``sgc_conv2d_nhwc_bf16x3`` (its `relu = 2`: ReLU, then the skip), everything else to ``sgc_conv2d_nhwc_ex_bf16x3``."""
+        ``sgc_conv2d_nhwc_bf16x3`` (its `relu = 2`: ReLU, then the skip), everything else to ``sgc_conv2d_nhwc_ex_bf16x3``; a
+        stride-2 layer over a map with an odd side to ``sgc_conv2d_nhwc_strided_bf16x3`` (output ceil(H / 2) x ceil(W / 2), the
+        ResNet stages: DESIGN.md 4.11)."""
         ops = ext.ops()
         N, H, W = nhw
-        onhw = (N, 2 * H, 2 * W) if self.transposed else (N, H // self.stride, W // self.stride)
+        s = self.stride
+        onhw = (N, 2 * H, 2 * W) if self.transposed else (N, (H + s - 1) // s, (W + s - 1) // s)
+        if s == 2 and not self.transposed and (H % 2 or W % 2):
+            y = ops.conv2d_nhwc_strided_bf16x3(x, self.w_hi, self.w_lo, nhw, self.k, stride=s, scale=self.scale, shift=self.shift,
+                                               residual=residual, relu=relu, relu_after_add=relu_after_add, out=out, col0=col0,
+                                               softmax_cols=softmax_cols)
+            return y, onhw
         if (self.stride == 1 and not self.transposed and out is None and not relu_after_add and softmax_cols == 0
                 and (residual is None or residual.shape[1] == self.w_hi.shape[1])):
             mode = (2 if residual is not None else 1) if relu else 0

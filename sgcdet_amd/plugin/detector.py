@@ -1,7 +1,9 @@
 """``SGCDet`` detector shell: the three calls of the reference that form the hot path.
 
-Reference: mmdet3d_plugin/models/detectors/SGCDet.py:61-129.  The 2D backbone (ResNet + FPN, mmdet -- not in the
-reference tree) is upstream of the path and is NOT built here: its configs are accepted and kept.  ``depth_head``
+Reference: mmdet3d_plugin/models/detectors/SGCDet.py:61-129.  The 2D backbone (mmdet's ResNet -- not in the reference tree) is
+NOT built by the constructor: its config is accepted and kept, and ``attach_backbone()`` builds it on request
+(plugin/resnet.py); with it attached, ``build_volume`` / ``simple_test`` / ``forward_train`` take the reference's ``batch``
+dict from images on.  ``depth_head``
 (``DepthNet_Fusion``, row f-2 of SURVEY.md section 8) IS built when configured: ``build_volume_from_fpn`` runs it on the
 finest FPN map + the images (SGCDet.py:71-85) and hands its depth distribution to the path -- in inference on the GPU its
 2-D CNNs run on the library's MFMA kernels and the distribution is channels-last in memory (plugin/depth_net.py), which
@@ -16,7 +18,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ..mmcv_lite import DETECTORS, build_head, build_neck
+from ..mmcv_lite import DETECTORS, build_backbone, build_head, build_neck
 
 
 @DETECTORS.register_module()
@@ -26,7 +28,9 @@ class SGCDet(nn.Module):
                  use_gt_dpt=False, depth_loss=False, occ_loss=False, lighting_augmentation=False):
         super().__init__()
         self.upstream_cfg = dict(backbone=backbone, neck=neck, depth_head=depth_head, head_2d=head_2d)
-        # the image FPN (row f-1): built when the config names the plain FPN; the backbone stays a config entry
+        # the image FPN (row f-1): built when the config names the plain FPN; the backbone stays a config entry until
+        # ``attach_backbone()`` is called
+        self.backbone = None
         self.neck = build_neck(neck) if isinstance(neck, dict) and neck.get("type") == "FPN" else None
         self.depth_head = build_head(depth_head) if depth_head is not None else None
         self.use_gt_dpt, self.depth_loss = use_gt_dpt, depth_loss
@@ -41,6 +45,58 @@ class SGCDet(nn.Module):
         self.train_cfg = train_cfg
         self.test_cfg = test_cfg
         self.occ_loss = occ_loss
+
+    # ---- the 2-D backbone: opt-in, images -> the maps the FPN reads (row f-0) --------------------------------------------
+    def attach_backbone(self, cfg=None):
+        """Build ``self.backbone`` from ``cfg`` (or from the ``backbone`` entry the constructor kept) and register it as a
+        submodule: ``state_dict()`` then carries the reference's ``backbone.*`` keys (a released checkpoint loads whole) and
+        ``optim.build_optimizer`` finds its 0.1 x lr group.  The constructor does not do this: a detector fed from feature
+        maps carries no backbone.  Returns ``self``."""
+        cfg = cfg if cfg is not None else self.upstream_cfg.get("backbone")
+        if cfg is None:
+            raise RuntimeError("SGCDet.attach_backbone: no backbone config was given and the detector was built without one")
+        self.backbone = build_backbone(cfg)
+        return self
+
+    def _need_backbone(self, who):
+        if self.backbone is None:
+            raise RuntimeError(f"SGCDet.{who}: no backbone is attached -- call attach_backbone() first, or feed feature maps "
+                               "(simple_test_from_features, build_volume_from_fpn, forward_train_from_fpn)")
+        if self.upstream_cfg.get("head_2d") is not None:
+            raise NotImplementedError("SGCDet: head_2d is not built (the SGCDet configs set none)")
+
+    def extract_img_feat(self, img):
+        """img [B, N, 3, H, W] -> FPN maps [[B, N, C, H_l, W_l], ...] (SGCDet.py:62-69, B = 1 as there)."""
+        self._need_backbone("extract_img_feat")
+        if img.shape[0] != 1:
+            raise NotImplementedError("SGCDet: batch size 1, as the reference's voxel head")
+        return self.image_features(self.backbone(img.reshape([-1] + list(img.shape)[2:])))
+
+    def build_volume(self, batch):
+        """SGCDet.build_volume (SGCDet.py:61-94): ``batch`` = dict(img [B,N,3,H,W], img_metas, depth_maps for ``use_gt_dpt``)
+        -> (volume, valid, features_2d = None, dpt_dist, occ)."""
+        self._need_backbone("build_volume")
+        x = self.extract_img_feat(batch["img"])
+        volume, valid, dpt_dist, occ = self.build_volume_from_fpn(x, batch["img"], batch["img_metas"], batch.get("depth_maps"))
+        return volume, valid, None, dpt_dist, occ
+
+    def simple_test(self, batch):
+        """SGCDet.simple_test (SGCDet.py:119-129): images -> ``bbox3d2result`` dicts."""
+        self._need_backbone("simple_test")
+        x = self.extract_img_feat(batch["img"])
+        dpt_dist = self.depth_distribution(x, batch["img"], batch["img_metas"], batch.get("depth_maps"))
+        return self.simple_test_from_features(x, batch["img_metas"], dpt_dist, as_results=True)
+
+    def forward_test(self, batch):
+        return self.simple_test(batch)
+
+    def forward_train(self, batch):
+        """SGCDet.forward_train (SGCDet.py:98-114): the losses of a batch from images on (the backbone runs its torch
+        formulation under autograd)."""
+        self._need_backbone("forward_train")
+        x = self.extract_img_feat(batch["img"])
+        return self.forward_train_from_fpn(x, batch["img"], batch["img_metas"], batch["gt_bboxes_3d"], batch["gt_labels_3d"],
+                                           batch.get("depth_maps"))
 
     def image_features(self, backbone_feats):
         """Backbone maps [[B*N, C_l, H_l, W_l], ...] -> [[B, N, C, H, W], ...] as SGCDet.py:67-69 with B = 1.  In eval mode on

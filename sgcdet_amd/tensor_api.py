@@ -811,12 +811,14 @@ class TensorOps:
                                                                Cout if ldy is None else ldy, col0, ldr, softmax_cols))
 
     def conv2d_nhwc_ex_bf16x3(self, x, w_hi, w_lo, nhw, ksize, stride=1, transposed=False, scale=None, shift=None,
-                              residual=None, relu=False, relu_after_add=False, out=None, col0=0, softmax_cols=0):
+                              residual=None, relu=False, relu_after_add=False, out=None, col0=0, softmax_cols=0, _any_size=False):
         """Strided / transposed 2-D convolution over channels-last rows (``sgc_conv2d_nhwc_ex_bf16x3``): x [N*H*W, Cin] ->
         [N*OH*OW, Cout]; k in {1,3} stride in {1,2} padding k//2, or ``transposed`` = ConvTranspose2d(3, stride 2, padding 1,
         output_padding 1).  Weights [k*k, Cout, Cin] split as ``split_operand``.  Epilogue: scale/shift, ``relu``,
         + ``residual`` [rows, >= Cout] (its own row pitch), ``relu_after_add``, softmax over the first ``softmax_cols`` columns.
-        ``out`` [rows, ldy] with ``col0``: the Cout columns land at [col0, col0 + Cout), the others are not touched."""
+        ``out`` [rows, ldy] with ``col0``: the Cout columns land at [col0, col0 + Cout), the others are not touched.
+        (``_any_size``: the body of ``conv2d_nhwc_strided_bf16x3``.)"""
+        entry = "sgc_conv2d_nhwc_strided_bf16x3" if _any_size else "sgc_conv2d_nhwc_ex_bf16x3"
         self._check(x=x, w_hi=w_hi, w_lo=w_lo, scale=scale, shift=shift, residual=residual, out=out)
         self._f32(x=x, scale=scale, shift=shift, residual=residual, out=out)
         if w_hi.dtype != torch.bfloat16 or w_lo.dtype != torch.bfloat16 or w_hi.shape != w_lo.shape:
@@ -828,9 +830,9 @@ class TensorOps:
             raise RuntimeError("conv2d_nhwc_ex_bf16x3: the transposed form is 3x3 stride 2")
         if rows != N * H * W or Cin2 != Cin or taps != ksize * ksize or stride not in (1, 2):
             raise RuntimeError("conv2d_nhwc_ex_bf16x3: inconsistent shapes")
-        if not transposed and stride == 2 and (H % 2 or W % 2):
+        if not transposed and stride == 2 and (H % 2 or W % 2) and not _any_size:
             raise RuntimeError("conv2d_nhwc_ex_bf16x3: a stride-2 layer needs even H and W")
-        OH, OW = (2 * H, 2 * W) if transposed else (H // stride, W // stride)
+        OH, OW = (2 * H, 2 * W) if transposed else ((H + stride - 1) // stride, (W + stride - 1) // stride)
         orows = N * OH * OW
         y = out if out is not None else torch.empty((orows, Cout), dtype=torch.float32, device=x.device)
         if y.dim() != 2 or y.shape[0] != orows or col0 < 0 or col0 + Cout > y.shape[1]:
@@ -843,10 +845,36 @@ class TensorOps:
         if not 0 <= softmax_cols <= Cout:
             raise RuntimeError("conv2d_nhwc_ex_bf16x3: softmax_cols outside [0, Cout]")
         flags = (1 if relu else 0) | (2 if relu_after_add else 0)
-        self._call("sgc_conv2d_nhwc_ex_bf16x3", x, w_hi, w_lo, scale, shift, residual, y, N, H, W, Cin, Cout, ksize, stride,
+        self._call(entry, x, w_hi, w_lo, scale, shift, residual, y, N, H, W, Cin, Cout, ksize, stride,
                    int(transposed), flags, y.shape[1], col0, residual.shape[1] if residual is not None else 0, softmax_cols,
                    _meta=dict(V=rows, Cin=Cin, Cout=Cout, taps=taps, OV=orows, stride=stride, transposed=bool(transposed)))
         return y
+
+    def conv2d_nhwc_strided_supported(self, nhw, Cin, Cout, ksize, stride=2, ldy=None, col0=0, ldr=0, softmax_cols=0):
+        N, H, W = nhw
+        return bool(self.lib._dll.sgc_conv2d_nhwc_strided_supported(N, H, W, Cin, Cout, ksize, stride, 0,
+                                                                    Cout if ldy is None else ldy, col0, ldr, softmax_cols))
+
+    def conv2d_nhwc_strided_bf16x3(self, x, w_hi, w_lo, nhw, ksize, stride=2, scale=None, shift=None, residual=None, relu=False,
+                                   relu_after_add=False, out=None, col0=0, softmax_cols=0):
+        """``conv2d_nhwc_ex_bf16x3`` (not transposed) for stride-2 layers over maps of any size
+        (``sgc_conv2d_nhwc_strided_bf16x3``): x [N*H*W, Cin] -> [N*ceil(H/2)*ceil(W/2), Cout], nn.Conv2d with padding k//2."""
+        return self.conv2d_nhwc_ex_bf16x3(x, w_hi, w_lo, nhw, ksize, stride=stride, scale=scale, shift=shift, residual=residual,
+                                          relu=relu, relu_after_add=relu_after_add, out=out, col0=col0, softmax_cols=softmax_cols,
+                                          _any_size=True)
+
+    def maxpool2d_nhwc(self, x, nhw):
+        """nn.MaxPool2d(3, stride 2, padding 1) over channels-last rows (``sgc_maxpool2d_nhwc``): x [N*H*W, C] ->
+        ([N*OH*OW, C], (N, OH, OW)) with OH = (H - 1) // 2 + 1."""
+        self._check(x=x)
+        self._f32(x=x)
+        N, H, W = nhw
+        if x.dim() != 2 or x.shape[0] != N * H * W:
+            raise RuntimeError("maxpool2d_nhwc: x must be [N*H*W, C]")
+        OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        y = torch.empty((N * OH * OW, x.shape[1]), dtype=torch.float32, device=x.device)
+        self._call("sgc_maxpool2d_nhwc", x, y, N, H, W, x.shape[1])
+        return y, (N, OH, OW)
 
     def conv2d_stem7_bf16x3(self, img, w_hi, w_lo, scale=None, shift=None, relu=True):
         """fp32 NCHW images [N, 3, H, W] -> channels-last rows [N*(H/2)*(W/2), 64] of the 7x7 stride-2 padding-3 stem
