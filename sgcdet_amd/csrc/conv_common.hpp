@@ -12,6 +12,10 @@ int device_cus();                // rows_gemm.hip: multiProcessorCount of the cu
 int rows_gemm_launch(const float *x, int64_t ldx, const uint16_t *w_hi, const uint16_t *w_lo, const float *scale,
                      const float *shift, const float *residual, void *y, const int32_t *m_dev, int M, int K, int N, int relu,
                      int hm_S, int hm_cm, int hm_bf16, hipStream_t st, float *zero_row = nullptr);
+// its gather form (sgc_pairs_geometry_linear_bf16x3, dfa3d_fwd.hip): row r of the A operand is sum_k gw[r][k] * x[go[r][k]][:]
+bool rows_gemm_gather_supported(int K, int N, int64_t x_rows, int64_t rows);
+int rows_gemm_gather_launch(const float *x, int64_t x_rows, const float *gw, const int32_t *go, const uint16_t *w_hi, const uint16_t *w_lo,
+                            const float *shift, float *y, const int32_t *m_dev, int M, int K, int N, hipStream_t st);
 
 struct ConvParams {
   const float *x;         // [IV, Cin] channels-last input volume

@@ -20,7 +20,7 @@
 // camera-major: neighbouring tiles hit the same camera's value map in one L2.
 #include <string.h>
 
-#include "common.hpp"
+#include "conv_common.hpp"
 #include "tuning.hpp"
 
 namespace sgc {
@@ -575,10 +575,6 @@ extern "C" int sgc_pairs_geometry_sample(const float *feat, const float *dist, c
 // GEMM is the same kernel): bit-identical results.
 // ---------------------------------------------------------------------------------------------
 namespace sgc {
-bool rows_gemm_gather_supported(int K, int N, int64_t x_rows, int64_t rows);
-int rows_gemm_gather_launch(const float *x, int64_t x_rows, const float *gw, const int32_t *go, const uint16_t *w_hi, const uint16_t *w_lo,
-                            const float *shift, float *y, const int32_t *m_dev, int M, int K, int N, hipStream_t st);
-
 __global__ __launch_bounds__(256) void pairs_geometry_desc_kernel(const float *__restrict__ dist, const float *__restrict__ ref_cam,
                                                                   const int32_t *__restrict__ pair_cam, const int32_t *__restrict__ pair_q,
                                                                   const int32_t *__restrict__ totals, int n_items, int Nq, int S, int H, int W,

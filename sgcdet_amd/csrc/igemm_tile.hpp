@@ -128,12 +128,7 @@ struct IgemmTile {
     for (int i = 0; i < ACH; ++i) {
       const float v[4] = {ra[i].x, ra[i].y, ra[i].z, ra[i].w};
       bf16x4 h, l;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const __bf16 hb = op_hi<NP>(v[e]);
-        h[e] = hb;
-        l[e] = op_lo<NP>(v[e], hb);
-      }
+      split4<NP>(v, h, l);
       const int o = a_row(i) * LDKH + c4 * 4;
       *reinterpret_cast<bf16x4 *>(a_hi + o) = h;
       if constexpr (NP == 3) *reinterpret_cast<bf16x4 *>(a_lo + o) = l;
@@ -240,7 +235,7 @@ struct IgemmTile {
       for (int j = 0; j < TN; ++j)
 #pragma unroll
         for (int k = 0; k < 16; ++k)
-          cs[(wm * (BM / WM) + i * 32 + (k & 3) + 8 * (k >> 2) + 4 * (lane >> 5)) * LDC + wn * (BN / WN) + j * 32 + (lane & 31)] =
+          cs[(wm * (BM / WM) + i * 32 + acc_row(k) + 4 * (lane >> 5)) * LDC + wn * (BN / WN) + j * 32 + (lane & 31)] =
               acc[i][j][k];
     __syncthreads();
     return cs;

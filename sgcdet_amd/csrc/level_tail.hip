@@ -9,7 +9,7 @@
 // i.e. what ran as six launches (row GEMM, scatter, LayerNorm, two 1x1x1 GEMMs, LayerNorm: ~80 us per level at
 // config 2, each of them at its launch-latency floor) with the [Nq, C] / [Nq, 2C] intermediates going through HBM four
 // times.  Here they stay in LDS:
-//   * a workgroup (C / 32 waves) owns 32 voxels; every GEMM stage uses the persistent row GEMM's scheme (rows_gemm.hip):
+//   * a workgroup (C / 32 waves) owns 32 voxels; every GEMM stage uses the persistent row GEMM's scheme (rows_core.hpp):
 //     a wave keeps the weights of its 32 output columns for a K chunk of C as MFMA B fragments in registers (loaded
 //     from L2 once per stage), A fragments come from a bf16 hi / lo image in LDS, 3 bf16 products per multiply-add;
 //   * stage outputs are written back to LDS in the form the next stage reads (fp32 rows for the LayerNorms and the
@@ -17,8 +17,7 @@
 //   * LayerNorm is the arithmetic of layer_norm_rows_kernel (common.hpp: ln_row_stats / ln_apply), one wave per row.
 // Every product, sum order and epilogue expression is that of the unfused kernels, so the fused level is
 // BIT-IDENTICAL to the six launches (tests/test_gpu_kernels.py checks it) -- it is a scheduling change, not a numerical one.
-#include "conv_common.hpp"
-#include "mma.hpp"
+#include "rows_core.hpp"
 
 namespace sgc {
 
@@ -85,29 +84,6 @@ __global__ __launch_bounds__(C * 2, 2) void level_tail_kernel(const LevelTailPar
       }
     }
   };
-  constexpr int PD = 3;                            // A fragments read PD k-steps ahead (see rows_gemm.hip)
-  auto multiply = [&](const __bf16 *hi, const __bf16 *lo, int pitch, int koff, f32x16 &acc) {
-    const __bf16 *a_hi = hi + fr * pitch + koff + fh * 8, *a_lo = lo + fr * pitch + koff + fh * 8;
-    bf16x8 ah[PD + 1], al[PD + 1];
-#pragma unroll
-    for (int kk = 0; kk < PD; ++kk) {
-      ah[kk] = *reinterpret_cast<const bf16x8 *>(a_hi + kk * 16);
-      if constexpr (NP == 3) al[kk] = *reinterpret_cast<const bf16x8 *>(a_lo + kk * 16);
-    }
-#pragma unroll
-    for (int kk = 0; kk < KS; ++kk) {
-      if (kk + PD < KS) {
-        ah[(kk + PD) % (PD + 1)] = *reinterpret_cast<const bf16x8 *>(a_hi + (kk + PD) * 16);
-        if constexpr (NP == 3) al[(kk + PD) % (PD + 1)] = *reinterpret_cast<const bf16x8 *>(a_lo + (kk + PD) * 16);
-      }
-      acc = mma_split<NP>(ah[kk % (PD + 1)], al[kk % (PD + 1)], bh[kk], bl[kk], acc);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  };
-  auto zero = [&](f32x16 &acc) {
-#pragma unroll
-    for (int k = 0; k < 16; ++k) acc[k] = 0.f;
-  };
   // LayerNorm of this wave's RPW rows of X; result back into X and, split, into the A image; `to_global`: the level's output
   auto layer_norm = [&](const float *g, const float *b, float eps, bool to_global, int q0) {
 #pragma unroll
@@ -161,20 +137,12 @@ __global__ __launch_bounds__(C * 2, 2) void level_tail_kernel(const LevelTailPar
       const int r = q < p.Nq ? p.row_of[q] : -1;
       const float4 v4 = r >= 0 ? *reinterpret_cast<const float4 *>(p.ctx + (int64_t)r * C + ld_c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
       const float v[4] = {v4.x, v4.y, v4.z, v4.w};
-      bf16x4 h, l;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const __bf16 hb = op_hi<NP>(v[e]);
-        h[e] = hb;
-        l[e] = op_lo<NP>(v[e], hb);
-      }
-      *reinterpret_cast<bf16x4 *>(A_hi + row * PA + ld_c4 * 4) = h;
-      *reinterpret_cast<bf16x4 *>(A_lo + row * PA + ld_c4 * 4) = l;
+      rows_stage_chunk<NP>(v, A_hi, LT_ROWS * PA, PA, row, ld_c4);
     }
     __syncthreads();
     f32x16 acc;
-    zero(acc);
-    multiply(A_hi, A_lo, PA, 0, acc);
+    rows_zero(acc);
+    rows_multiply<KS, NP>(A_hi, LT_ROWS * PA, PA, 0, fr, fh, bh, bl, acc);
     {
       const float sh = p.bo[col];
       float *xb = X + 4 * fh * C + col;            // one per-lane base; the row part of every address is an immediate offset
@@ -182,8 +150,8 @@ __global__ __launch_bounds__(C * 2, 2) void level_tail_kernel(const LevelTailPar
 #pragma unroll
       for (int k = 0; k < 16; ++k) {
         float v = acc[k] + sh;
-        v = rv[(k & 3) + 8 * (k >> 2)] >= 0 ? v : 0.f;     // voxels no camera sees keep the zero row of the reference's slot scatter
-        xb[((k & 3) + 8 * (k >> 2)) * C] = v;
+        v = rv[acc_row(k)] >= 0 ? v : 0.f;     // voxels no camera sees keep the zero row of the reference's slot scatter
+        xb[acc_row(k) * C] = v;
       }
     }
     __syncthreads();
@@ -199,8 +167,8 @@ __global__ __launch_bounds__(C * 2, 2) void level_tail_kernel(const LevelTailPar
         __builtin_amdgcn_sched_barrier(0);           // not above the multiply that still reads the first half's fragments
         load_B(p.w1_hi, p.w1_lo, F, NW + wid, KS, 0);
       }
-      zero(acc);
-      multiply(A_hi, A_lo, PA, 0, acc);
+      rows_zero(acc);
+      rows_multiply<KS, NP>(A_hi, LT_ROWS * PA, PA, 0, fr, fh, bh, bl, acc);
       const int hc = pass * C + col;
       const float sh = p.b1[hc];
       __bf16 *hh = H_hi + 4 * fh * PH + hc, *hl = H_lo + 4 * fh * PH + hc;
@@ -208,18 +176,18 @@ __global__ __launch_bounds__(C * 2, 2) void level_tail_kernel(const LevelTailPar
       for (int k = 0; k < 16; ++k) {
         const float v = fmaxf(acc[k] + sh, 0.f);
         const __bf16 hb = op_hi<NP>(v);
-        hh[((k & 3) + 8 * (k >> 2)) * PH] = hb;
-        hl[((k & 3) + 8 * (k >> 2)) * PH] = op_lo<NP>(v, hb);
+        hh[acc_row(k) * PH] = hb;
+        hl[acc_row(k) * PH] = op_lo<NP>(v, hb);
       }
     }
     __syncthreads();
     // ---- x2 = W2 h + b2 + x1: one accumulator chain over the two K chunks (k ascending, as the unfused K = 2C GEMM) ----
-    zero(acc);
+    rows_zero(acc);
 #pragma unroll
     for (int kc = 0; kc < 2; ++kc) {
       __builtin_amdgcn_sched_barrier(0);             // one set of weight fragments lives at a time (128 VGPRs at C = 256)
       load_B(p.w2_hi, p.w2_lo, C, wid, 2 * KS, kc * KS);
-      multiply(H_hi, H_lo, PH, kc * C, acc);
+      rows_multiply<KS, NP>(H_hi, LT_ROWS * PH, PH, kc * C, fr, fh, bh, bl, acc);
     }
     {
       const float sh = p.b2[col];
@@ -227,8 +195,8 @@ __global__ __launch_bounds__(C * 2, 2) void level_tail_kernel(const LevelTailPar
 #pragma unroll
       for (int k = 0; k < 16; ++k) {
         float v = acc[k] + sh;
-        v += xb[((k & 3) + 8 * (k >> 2)) * C];
-        xb[((k & 3) + 8 * (k >> 2)) * C] = v;
+        v += xb[acc_row(k) * C];
+        xb[acc_row(k) * C] = v;
       }
     }
     __syncthreads();
@@ -244,18 +212,8 @@ static int launch_level_tail(const LevelTailParams &p, hipStream_t st) {
   static std::atomic<uint64_t> attr_done{0};
   ensure_dynamic_lds((const void *)level_tail_kernel<C, NP>, smem, attr_done);
   const int ntiles = ceil_div(p.Nq, LT_ROWS);
-  int cus = 256;
-  {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    static std::atomic<int> cached{0};
-    if (cached.load() == 0 && hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess &&
-        prop.multiProcessorCount > 0)
-      cached.store(prop.multiProcessorCount);
-    if (cached.load() > 0) cus = cached.load();
-  }
   const int per_cu = C == 256 ? 1 : 2;
-  const int grid = ntiles < cus * per_cu ? ntiles : cus * per_cu;
+  const int grid = ntiles < device_cus() * per_cu ? ntiles : device_cus() * per_cu;
   hipLaunchKernelGGL((level_tail_kernel<C, NP>), dim3(grid), dim3(C * 2), smem, st, p);
   return check_launch("level_tail_kernel");
 }

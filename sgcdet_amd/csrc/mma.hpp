@@ -36,6 +36,24 @@ __device__ __forceinline__ __bf16 op_lo(float v, __bf16 hi) {
   if constexpr (NP == 3) return (__bf16)(v - (float)hi);
   else return __builtin_bit_cast(__bf16, (unsigned short)0);
 }
+// four consecutive floats as the 8-byte pieces of the hi and lo planes (built in locals: through the references every element
+// store may alias v, and the packed conversions are lost)
+template <int NP>
+__device__ __forceinline__ void split4(const float (&v)[4], bf16x4 &h, bf16x4 &l) {
+  bf16x4 h4, l4;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const __bf16 hb = op_hi<NP>(v[e]);
+    h4[e] = hb;
+    l4[e] = op_lo<NP>(v[e], hb);
+  }
+  h = h4;
+  l = l4;
+}
+// 32x32 accumulator (lane = column): the row of element k within a lane half; lanes 32-63 sit 4 rows below.  (The epilogues of
+// conv3d_halo.hpp, conv3d_igemm.hip, conv2d_image.hip and conv3d_wgrad.hip spell the sum out inside their address expressions: as
+// a call it associates differently and their code changes -- profiles/r14_rows_core.md)
+__host__ __device__ constexpr int acc_row(int k) { return (k & 3) + 8 * (k >> 2); }
 // the hi * hi product (the only one of the one-product modes)
 template <int NP>
 __device__ __forceinline__ f32x16 mma_hh(bf16x8 a, bf16x8 b, f32x16 c) {

@@ -64,12 +64,7 @@ __global__ __launch_bounds__(512) void rows_blockdiag_kernel(const BdParams p) {
     for (int i = 0; i < 16; ++i) {
       const float v[4] = {ra[i].x, ra[i].y, ra[i].z, ra[i].w};
       bf16x4 h, l;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const __bf16 hb = op_hi<NP>(v[e]);
-        h[e] = hb;
-        l[e] = op_lo<NP>(v[e], hb);
-      }
+      split4<NP>(v, h, l);
       const int o = (2 * i + half) * BD_PITCH + col * 4;
       *reinterpret_cast<bf16x4 *>(a_hi + o) = h;
       if constexpr (NP == 3) *reinterpret_cast<bf16x4 *>(a_lo + o) = l;
@@ -107,7 +102,7 @@ __global__ __launch_bounds__(512) void rows_blockdiag_kernel(const BdParams p) {
     if (col < NH) {
 #pragma unroll
       for (int k = 0; k < 16; ++k) {
-        const int row = tile * 32 + (k & 3) + 8 * (k >> 2) + 4 * half;
+        const int row = tile * 32 + acc_row(k) + 4 * half;
         if (row < rows) p.y[(size_t)row * YS + g * NH + col] = acc[k] + bias;
       }
     }

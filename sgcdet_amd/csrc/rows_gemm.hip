@@ -29,24 +29,18 @@
 // The k order and the product order are those of conv3d_igemm_bf16x3_kernel: both kernels give identical bits.
 #include <stdlib.h>
 
-#include "conv_common.hpp"
-#include "tuning.hpp"
-#include "mma.hpp"
-#include "diag.hpp"
+#include "rows_core.hpp"
 
 namespace sgc {
 
 // rows_diag    TIMING EXPERIMENTS ONLY, honoured only with SGC_DIAG=1 in the environment (results are then
 //              invalid): bit 0 = stores dropped by the range check, bit 1 = loads dropped (zeros), bit 2 = no MFMA
-// rows_cu_pct  the kernel is memory-bound: with scenes in flight the CUs it leaves serve MFMA kernels
-// rows_depth   8-wave form: 1 / 2 = lockstep with that many tiles in flight ahead of the one being multiplied,
-//              0 = staggered halves (waves 4-7 half a period behind waves 0-3); the 4-wave form (two workgroups
-//              per CU) is lockstep, 1 ahead.  Interleaved A/B on the 204,800 x 256 -> 256 Linear (3 rounds x 40
-//              launches): lockstep-1 90-93 us row-major / 94-98 head-major, lockstep-2 92-93 / 98-101, staggered
-//              96-100 / 97-104 (in-kernel stamps: a staging phase issues ~350 instructions per wave and tile and
-//              slows the partner wave's MFMA chain from 1536 to 2000-3000 cycles, so separating the phases in
-//              time does not pay); the memory-only form of the kernel (no MFMA) takes 80 us = 5.2 TB/s
-
+// rows_cu_pct  see persistent_stripes (rows_core.hpp)
+// rows_depth   8-wave form: 2 = two tiles in flight ahead of the one being multiplied, anything else = one; the 4-wave
+//              form (two workgroups per CU) and the one-product modes run one ahead.  A staggered-halves form (waves 4-7
+//              half a period behind waves 0-3) is gone: interleaved on the 204,800 x 256 -> 256 Linear it took 96-100 us
+//              row-major against 90-93 for one tile ahead and 92-93 for two; the memory-only form of the kernel (no
+//              MFMA) takes 80 us = 5.2 TB/s
 
 struct RowsGemmParams {
   const float *x;              // [M, K] rows, row stride ldx floats
@@ -61,7 +55,6 @@ struct RowsGemmParams {
   int hm_S, hm_cm, hm_bf16;
   int ncg;                     // column groups of NW * 32 columns
   int diag;                    // see g_tune_rows_diag
-  unsigned long long *stamps;  // diagnostic builds only
   int64_t y_bytes;             // head-major output: bytes of the whole buffer (the range the stores are checked against)
   float *zero_row;             // optional: N floats the launch sets to zero (the all-zero row behind the value map the wave gather
                                // points out-of-image corners at, sgc_linear_rows_zrow_bf16x3) -- by workgroup 0, before its tiles
@@ -71,11 +64,6 @@ struct RowsGemmParams {
   const int32_t *go;           // [M][4] row of x of each corner (a valid row also where the weight is 0)
   int64_t x_rows;              // rows of x (the whole feature map), GATHER only
 };
-
-constexpr int RG_ROWS = 32;
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-constexpr unsigned RG_OOB = 0xfffffff0u;    // a byte offset no buffer of < 4 GiB reaches: the load returns 0, the store is dropped
 
 // EPI: 0 = y = acc * scale + shift (optional relu), row-major; 1 = head-major fp32 store (value_proj); 2 = row-major with
 // residual; 3 = head-major bf16 store (opt-in storage mode)
@@ -120,31 +108,21 @@ __global__ __launch_bounds__(NW * 64, 2) void rows_gemm_bf16x3_kernel(const Rows
   const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float *>(EPI == 2 ? p.residual : p.x), 0, (int)(unsigned)(EPI == 2 ? (int64_t)Mrows * p.N * 4 : 0), 0x00020000);
 
-  // ---- weights: all of K for this wave's 32 columns, as B fragments in registers ----
   bf16x8 bh[KS], bl[KS];
-  {
-    const __bf16 *wh = p.w_hi + (int64_t)col * K + fh * 8, *wl = p.w_lo + (int64_t)col * K + fh * 8;
-#pragma unroll
-    for (int kk = 0; kk < KS; ++kk) {
-      bh[kk] = *reinterpret_cast<const bf16x8 *>(wh + kk * 16);
-      if constexpr (NP == 3) bl[kk] = *reinterpret_cast<const bf16x8 *>(wl + kk * 16);
-    }
-  }
+  rows_load_B<KS, NP>(p.w_hi, p.w_lo, col, fh, bh, bl);
   const float sc = p.scale ? p.scale[col] : 1.f, sh = p.shift ? p.shift[col] : 0.f;
-  const bool relu = p.relu != 0, relu1 = p.relu == 1, relu2 = p.relu == 2;
+  // relu modes (conv3d.hip's): 1 = relu(y + residual), 2 = relu(y) + residual; without a residual both are relu(y)
+  const bool relu_before = EPI == 2 ? p.relu == 2 : p.relu != 0, relu_after = p.relu == 1;
 
-  // Staging deal.  NTL threads cooperate on RL rows of a tile: all NT threads on all 32 rows, or -- staggered form
-  // (DEPTH == 0, 8 waves) -- each half of the workgroup (waves 0-3 / 4-7) on its own 16 rows.  Chunk i of a thread:
-  // f = tl + i * NTL -> (row, 16-byte chunk) = (tl / K4 + i * (NTL / K4), tl % K4): one per-lane offset plus a SCALAR
-  // multiple of the row pitch per chunk (made opaque per call: not hoisted into CH long-lived VGPRs)
-  constexpr bool STAG = DEPTH == 0;
-  static_assert(!STAG || NW == 8, "the staggered form pairs waves w and w + 4 of an 8-wave workgroup");
-  constexpr int NTL = STAG ? NT / 2 : NT, RL = STAG ? RG_ROWS / 2 : RG_ROWS;
-  static_assert(NTL % K4 == 0 && RL * K4 / NTL == CH, "chunks of a thread must share their column");
-  const int late = STAG ? __builtin_amdgcn_readfirstlane(wid >> 2) : 0;      // 1: waves 4-7, half a period behind
-  const int tl = STAG ? (tid & (NTL - 1)) : tid;
-  const int ld_row = tl / K4 + late * RL, ld_c4 = tl % K4;
-  // A tile in flight: CH 16-byte chunks per thread -- or, GATHER, the four corner rows' chunks and their weights
+  // Staging deal: all NT threads cooperate on the 32 rows of a tile.  Chunk i of a thread: f = tid + i * NT -> (row, 16-byte
+  // chunk) = (tid / K4 + i * (NT / K4), tid % K4): one per-lane offset plus a SCALAR multiple of the row pitch per chunk (made
+  // opaque per call: not hoisted into CH long-lived VGPRs)
+  static_assert(NT % K4 == 0, "chunks of a thread must share their column");
+  constexpr int RSTEP = NT / K4;
+  const int ld_row = tid / K4, ld_c4 = tid % K4;
+  // A tile in flight: CH 16-byte chunks per thread -- or, GATHER, the four corner rows' chunks and their weights.  The gather
+  // branches below are this kernel's own copy of rows_gather_request / rows_gather_build (rows_core.hpp): built from the helpers the
+  // K = 128 gather form waited for its corner rows in coarser steps and ran 4.5 % slower (profiles/r14_rows_core.md)
   constexpr int TV = GATHER ? 4 * CH + CH : CH;
   auto load_tile = [&](int t, float4 (&ra)[TV]) {
     int ldx4 = (int)p.ldx * 4;
@@ -152,7 +130,7 @@ __global__ __launch_bounds__(NW * 64, 2) void rows_gemm_bf16x3_kernel(const Rows
     if constexpr (GATHER) {
 #pragma unroll
       for (int i = 0; i < CH; ++i) {
-        const unsigned doff = t < ntiles ? (unsigned)(t * RG_ROWS + ld_row + i * (NTL / K4)) * 16u : RG_OOB;
+        const unsigned doff = t < ntiles ? (unsigned)(t * RG_ROWS + ld_row + i * RSTEP) * 16u : RG_OOB;
         const u32x4 o = __builtin_amdgcn_raw_buffer_load_b128(gor, doff, 0, 0);
         const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(gwr, doff, 0, 0);
         ra[4 * CH + i] = make_float4(__uint_as_float(w[0]), __uint_as_float(w[1]), __uint_as_float(w[2]), __uint_as_float(w[3]));
@@ -167,19 +145,17 @@ __global__ __launch_bounds__(NW * 64, 2) void rows_gemm_bf16x3_kernel(const Rows
     const unsigned base = t < ntiles ? (unsigned)(t * RG_ROWS + ld_row) * (unsigned)ldx4 + ld_c4 * 16 : RG_OOB;
 #pragma unroll
     for (int i = 0; i < CH; ++i) {
-      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(xr, t < ntiles ? base + i * (NTL / K4) * ldx4 : RG_OOB, 0, 0);
+      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(xr, t < ntiles ? base + i * RSTEP * ldx4 : RG_OOB, 0, 0);
       ra[i] = make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
     }
   };
   auto split_tile = [&](const float4 (&ra)[TV], int buf) {
-    __bf16 *a_hi = lds + buf * 2 * PLANE, *a_lo = a_hi + PLANE;
+    __bf16 *a_hi = lds + buf * 2 * PLANE;
 #pragma unroll
     for (int i = 0; i < CH; ++i) {
-      const int row = ld_row + i * (NTL / K4), c4 = ld_c4;
       float v[4];
       if constexpr (GATHER) {
-        // the geometry sample's arithmetic (dfa3d_fwd_kernel<kPairsGeom>: acc += w[k] * v[k] over the corners in order, contracted
-        // to fmas): the staged row is the value sgc_pairs_geometry_sample would have written, bit for bit
+        // the geometry sample's arithmetic, corner by corner in order, as rows_gather_build has it
         const float wk[4] = {ra[4 * CH + i].x, ra[4 * CH + i].y, ra[4 * CH + i].z, ra[4 * CH + i].w};
         v[0] = v[1] = v[2] = v[3] = 0.f;
 #pragma unroll
@@ -190,42 +166,13 @@ __global__ __launch_bounds__(NW * 64, 2) void rows_gemm_bf16x3_kernel(const Rows
       } else {
         v[0] = ra[i].x; v[1] = ra[i].y; v[2] = ra[i].z; v[3] = ra[i].w;
       }
-      bf16x4 h, l;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const __bf16 hb = op_hi<NP>(v[e]);
-        h[e] = hb;
-        l[e] = op_lo<NP>(v[e], hb);
-      }
-      *reinterpret_cast<bf16x4 *>(a_hi + row * PITCH + c4 * 4) = h;
-      if constexpr (NP == 3) *reinterpret_cast<bf16x4 *>(a_lo + row * PITCH + c4 * 4) = l;
+      rows_stage_chunk<NP>(v, a_hi, PLANE, PITCH, ld_row + i * RSTEP, ld_c4);
     }
   };
-  // A fragments are read PD k-steps ahead of the MFMAs that use them (ring of PD + 1 register slots, static indices
-  // after unrolling); the scheduling barrier per step keeps that distance in the emitted code (left alone, the
-  // compiler issues each read one step ahead: ~96 MFMA cycles of cover for an LDS round trip, which a single wave per
-  // SIMD -- the staggered form -- cannot hide)
-  constexpr int PD = 3;
   auto multiply = [&](int buf, f32x16 &acc) {
-    const __bf16 *a_hi = lds + buf * 2 * PLANE + fr * PITCH + fh * 8, *a_lo = a_hi + PLANE;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) acc[k] = 0.f;
+    rows_zero(acc);
     if (p.diag & 4) return;
-    bf16x8 ah[PD + 1], al[PD + 1];
-#pragma unroll
-    for (int kk = 0; kk < PD; ++kk) {
-      ah[kk] = *reinterpret_cast<const bf16x8 *>(a_hi + kk * 16);
-      if constexpr (NP == 3) al[kk] = *reinterpret_cast<const bf16x8 *>(a_lo + kk * 16);
-    }
-#pragma unroll
-    for (int kk = 0; kk < KS; ++kk) {
-      if (kk + PD < KS) {
-        ah[(kk + PD) % (PD + 1)] = *reinterpret_cast<const bf16x8 *>(a_hi + (kk + PD) * 16);
-        if constexpr (NP == 3) al[(kk + PD) % (PD + 1)] = *reinterpret_cast<const bf16x8 *>(a_lo + (kk + PD) * 16);
-      }
-      acc = mma_split<NP>(ah[kk % (PD + 1)], al[kk % (PD + 1)], bh[kk], bl[kk], acc);
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    rows_multiply<KS, NP>(lds + buf * 2 * PLANE, PLANE, PITCH, 0, fr, fh, bh, bl, acc);
   };
   // head-major constants: row m = cam * S + s, column = head * cm + j  ->  [cam][head][s][cm]
   constexpr bool HM = EPI == 1 || EPI == 3;
@@ -246,7 +193,7 @@ __global__ __launch_bounds__(NW * 64, 2) void rows_gemm_bf16x3_kernel(const Rows
       const int live = Mrows - m0 - 4 * fh;
 #pragma unroll
       for (int k = 0; k < 16; ++k) {
-        const int r = (k & 3) + 8 * (k >> 2);                      // row - 4 * fh
+        const int r = acc_row(k);                                  // row - 4 * fh
         unsigned off = base + r * cme;
         off += r >= rows_left ? jump : 0u;
         off = r < live ? off : RG_OOB;
@@ -255,32 +202,7 @@ __global__ __launch_bounds__(NW * 64, 2) void rows_gemm_bf16x3_kernel(const Rows
         else __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), yr, off, 0, 0);
       }
     } else {
-      // row offsets as SCALAR multiples of the row pitch added to one per-lane base: the pitch is made opaque per call
-      // so that the 16 offsets are not hoisted out of the tile loop into 16 long-lived VGPRs (the kernel sits at the
-      // 256-register limit of two waves per SIMD)
-      int n4 = p.N * 4;
-      asm volatile("" : "+s"(n4));
-      float res[16];
-      const unsigned base = (unsigned)(m0 + 4 * fh) * (unsigned)n4 + col * 4;
-      if constexpr (EPI == 2) {
-#pragma unroll
-        for (int k = 0; k < 16; ++k)
-          res[k] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rr, base + ((k & 3) + 8 * (k >> 2)) * n4, 0, 0));
-      }
-#pragma unroll
-      for (int k = 0; k < 16; ++k) {
-        float v = acc[k] * sc;                              // two roundings (product, then sum) like the staged epilogue of
-        asm volatile("" : "+v"(v));                          // conv3d.hip and the oracle's plain C: the empty asm keeps the
-        v += sh;                                             // compiler from contracting them into one fma
-        if constexpr (EPI == 2) {
-          v = relu2 ? fmaxf(v, 0.f) : v;
-          v += res[k];
-          v = relu1 ? fmaxf(v, 0.f) : v;
-        } else {
-          v = relu ? fmaxf(v, 0.f) : v;
-        }
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), yr, base + ((k & 3) + 8 * (k >> 2)) * n4, 0, 0);
-      }
+      rows_store_rowmajor<EPI == 2>(acc, yr, rr, m0, fh, col, p.N, sc, sh, relu_before, relu_after);
     }
   };
 
@@ -293,53 +215,7 @@ __global__ __launch_bounds__(NW * 64, 2) void rows_gemm_bf16x3_kernel(const Rows
   f32x16 acc;
   const int n = (ntiles - stripe + nstripes - 1) / nstripes;     // tiles of this workgroup, >= 1
   int t = stripe;                                                // tile multiplied in the current iteration
-  if constexpr (STAG) {
-    // Staggered halves.  Waves w and w + 4 share a SIMD; a period has two half-periods separated by a barrier: in the
-    // first, waves 0-3 multiply tile i while waves 4-7 stage (store tile i - 1, split their 16 rows of tile i + 1, load
-    // tile i + 2); in the second they swap.  Each SIMD then always holds one wave in its MFMA chain and one in the
-    // VALU / LDS-write / memory-issue part, which a lockstep schedule (both waves multiply, then both stage) serialises
-    // (measured on the 204,800-row Linear: staging 30 us + MFMA 33 us + memory, all additive).  Two LDS buffers are
-    // enough: the half of tile i + 1 staged by waves 4-7 during the first half-period lands in the buffer of tile
-    // i - 1, whose last reader (their own multiply) finished a barrier earlier.
-    float4 r0[TV];
-    RG_STAMP_PTR(p, wid, late);
-    load_tile(t, r0);
-    split_tile(r0, 0);
-    load_tile(t + nstripes, r0);
-    __syncthreads();
-    for (int i = 0; i < n; ++i) {
-      RG_STAMP(0);
-      if (!late) {
-        multiply(i & 1, acc);
-        asm volatile("" :: "v"(acc[0]));
-        RG_STAMP(1);
-      } else {
-        if (i > 0) store_tile(t - nstripes, acc);
-        RG_STAMP(1);
-        split_tile(r0, (i + 1) & 1);
-        RG_STAMP(2);
-        load_tile(t + 2 * nstripes, r0);
-        RG_STAMP(3);
-      }
-      __syncthreads();
-      RG_STAMP(4);
-      if (!late) {
-        split_tile(r0, (i + 1) & 1);
-        RG_STAMP(5);
-        load_tile(t + 2 * nstripes, r0);
-        store_tile(t, acc);
-        RG_STAMP(6);
-      } else {
-        multiply(i & 1, acc);
-        asm volatile("" :: "v"(acc[0]));
-        RG_STAMP(5);
-      }
-      t += nstripes;
-      __syncthreads();
-      RG_STAMP(7);
-    }
-    if (late) store_tile(t - nstripes, acc);
-  } else if constexpr (DEPTH == 2) {
+  if constexpr (DEPTH == 2) {
     float4 r0[TV], r1[TV];                 // tile j of this workgroup lives in set j & 1 until it is split
     load_tile(t, r0);
     load_tile(t + nstripes, r1);
@@ -429,48 +305,15 @@ __global__ __launch_bounds__(512) void rows_gemm_gather_pc_kernel(const RowsGemm
     const int col = wid * 32 + fr;
     const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, (int)(unsigned)((int64_t)Mrows * p.N * 4), 0x00020000);
     bf16x8 bh[KS], bl[KS];
-    {
-      const __bf16 *wh = p.w_hi + (int64_t)col * K + fh * 8, *wl = p.w_lo + (int64_t)col * K + fh * 8;
-#pragma unroll
-      for (int kk = 0; kk < KS; ++kk) {
-        bh[kk] = *reinterpret_cast<const bf16x8 *>(wh + kk * 16);
-        if constexpr (NP == 3) bl[kk] = *reinterpret_cast<const bf16x8 *>(wl + kk * 16);
-      }
-    }
+    rows_load_B<KS, NP>(p.w_hi, p.w_lo, col, fh, bh, bl);
     const float sc = p.scale ? p.scale[col] : 1.f, sh = p.shift ? p.shift[col] : 0.f;
-    constexpr int PD = 3;
     int t = stripe;
     for (int i = 0; i < n; ++i, t += nstripes) {
       __syncthreads();                                           // tile i is in buffer i & 1
-      const __bf16 *a_hi = lds + (i & 1) * 2 * PLANE + fr * PITCH + fh * 8, *a_lo = a_hi + PLANE;
       f32x16 acc;
-#pragma unroll
-      for (int k = 0; k < 16; ++k) acc[k] = 0.f;
-      bf16x8 ah[PD + 1], al[PD + 1];
-#pragma unroll
-      for (int kk = 0; kk < PD; ++kk) {
-        ah[kk] = *reinterpret_cast<const bf16x8 *>(a_hi + kk * 16);
-        if constexpr (NP == 3) al[kk] = *reinterpret_cast<const bf16x8 *>(a_lo + kk * 16);
-      }
-#pragma unroll
-      for (int kk = 0; kk < KS; ++kk) {
-        if (kk + PD < KS) {
-          ah[(kk + PD) % (PD + 1)] = *reinterpret_cast<const bf16x8 *>(a_hi + (kk + PD) * 16);
-          if constexpr (NP == 3) al[(kk + PD) % (PD + 1)] = *reinterpret_cast<const bf16x8 *>(a_lo + (kk + PD) * 16);
-        }
-        acc = mma_split<NP>(ah[kk % (PD + 1)], al[kk % (PD + 1)], bh[kk], bl[kk], acc);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      int n4 = p.N * 4;
-      asm volatile("" : "+s"(n4));
-      const unsigned base = (unsigned)(t * RG_ROWS + 4 * fh) * (unsigned)n4 + col * 4;
-#pragma unroll
-      for (int k = 0; k < 16; ++k) {
-        float v = acc[k] * sc;                              // two roundings, as the plain kernel's epilogue
-        asm volatile("" : "+v"(v));
-        v += sh;
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), yr, base + ((k & 3) + 8 * (k >> 2)) * n4, 0, 0);
-      }
+      rows_zero(acc);
+      rows_multiply<KS, NP>(lds + (i & 1) * 2 * PLANE, PLANE, PITCH, 0, fr, fh, bh, bl, acc);
+      rows_store_rowmajor<false>(acc, yr, yr, t * RG_ROWS, fh, col, p.N, sc, sh, false, false);
     }
     __syncthreads();                                             // the producers' last barrier
     return;
@@ -482,45 +325,8 @@ __global__ __launch_bounds__(512) void rows_gemm_gather_pc_kernel(const RowsGemm
   const __amdgpu_buffer_rsrc_t gwr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.gw), 0, (int)(unsigned)((int64_t)Mrows * 16), 0x00020000);
   const __amdgpu_buffer_rsrc_t gor = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t *>(p.go), 0, (int)(unsigned)((int64_t)Mrows * 16), 0x00020000);
   float4 rv[4 * CH], rw[CH];
-  auto request = [&](int t) {
-    int ldx4 = (int)p.ldx * 4;
-    asm volatile("" : "+s"(ldx4));
-#pragma unroll
-    for (int i = 0; i < CH; ++i) {
-      const unsigned doff = t < ntiles ? (unsigned)(t * RG_ROWS + ld_row + i * (NTP / K4)) * 16u : RG_OOB;
-      const u32x4 o = __builtin_amdgcn_raw_buffer_load_b128(gor, doff, 0, 0);
-      const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(gwr, doff, 0, 0);
-      rw[i] = make_float4(__uint_as_float(w[0]), __uint_as_float(w[1]), __uint_as_float(w[2]), __uint_as_float(w[3]));
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(xr, o[k] * (unsigned)ldx4 + ld_c4 * 16, 0, 0);
-        rv[4 * i + k] = make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
-      }
-    }
-  };
-  auto build = [&](int buf) {
-    __bf16 *a_hi = lds + buf * 2 * PLANE, *a_lo = a_hi + PLANE;
-#pragma unroll
-    for (int i = 0; i < CH; ++i) {
-      const int row = ld_row + i * (NTP / K4);
-      const float wk[4] = {rw[i].x, rw[i].y, rw[i].z, rw[i].w};
-      float v[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        v[0] = __builtin_fmaf(wk[k], rv[4 * i + k].x, v[0]); v[1] = __builtin_fmaf(wk[k], rv[4 * i + k].y, v[1]);
-        v[2] = __builtin_fmaf(wk[k], rv[4 * i + k].z, v[2]); v[3] = __builtin_fmaf(wk[k], rv[4 * i + k].w, v[3]);
-      }
-      bf16x4 h, l;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const __bf16 hb = op_hi<NP>(v[e]);
-        h[e] = hb;
-        l[e] = op_lo<NP>(v[e], hb);
-      }
-      *reinterpret_cast<bf16x4 *>(a_hi + row * PITCH + ld_c4 * 4) = h;
-      if constexpr (NP == 3) *reinterpret_cast<bf16x4 *>(a_lo + row * PITCH + ld_c4 * 4) = l;
-    }
-  };
+  auto request = [&](int t) { rows_gather_request<CH, NTP / K4>(xr, gor, gwr, t < ntiles, t * RG_ROWS + ld_row, ld_c4, p.ldx, rv, rw); };
+  auto build = [&](int buf) { rows_gather_build<NP, CH, NTP / K4>(rv, rw, lds + buf * 2 * PLANE, PLANE, PITCH, ld_row, ld_c4); };
   int t = stripe;
   request(t);
   build(0);
@@ -535,28 +341,37 @@ __global__ __launch_bounds__(512) void rows_gemm_gather_pc_kernel(const RowsGemm
   __syncthreads();
 }
 
-template <int K, int NW, int DEPTH, int EPI, int NP>
-static int launch_rows_gemm_np(const RowsGemmParams &p, int grid, hipStream_t st) {
-  constexpr int smem = 2 * 2 * RG_ROWS * (K + 8) * (int)sizeof(uint16_t);
-  static std::atomic<uint64_t> attr_done{0};
-  ensure_dynamic_lds((const void *)rows_gemm_bf16x3_kernel<K, NW, DEPTH, EPI, NP>, smem, attr_done);
-  hipLaunchKernelGGL((rows_gemm_bf16x3_kernel<K, NW, DEPTH, EPI, NP>), dim3(grid), dim3(NW * 64), smem, st, p);
-  return check_launch("rows_gemm_bf16x3_kernel");
+// host: f(std::integral_constant<int, V>) for the V of the list that equals v -- a run-time value as a template argument
+template <int... Vs, class F>
+static int with_value(int v, F &&f) {
+  int rc = SGC_EUNSUP;
+  ((v == Vs ? (rc = f(std::integral_constant<int, Vs>{}), 0) : 0), ...);
+  return rc;
 }
 
-template <int K, int NW, int DEPTH, int EPI>
-static int launch_rows_gemm_e(const RowsGemmParams &p, int grid, hipStream_t st) {
-  return with_products(g_conv_products, [&](auto np) {      // single-product modes: the lockstep-1 form
-    return launch_rows_gemm_np<K, NW, np() == 3 ? DEPTH : 1, EPI, np()>(p, grid, st);
+// One dispatch over (K, NW, DEPTH, EPI) and the arithmetic mode.  Two tiles ahead exists for the 8-wave three-product form only.
+static int launch_rows_gemm(const RowsGemmParams &p, int K, int nw, int grid, hipStream_t st) {
+  const int epi = p.hm_cm > 0 ? (p.hm_bf16 ? 3 : 1) : p.residual ? 2 : 0;
+  const int depth = (nw == 8 && g_tune_rows_depth == 2 && g_conv_products == 3) ? 2 : 1;
+  return with_value<128, 256>(K, [&](auto k) {
+    return with_value<4, 8>(nw, [&](auto w) {
+      return with_value<1, 2>(depth, [&](auto d) {
+        return with_value<0, 1, 2, 3>(epi, [&](auto e) {
+          return with_products(g_conv_products, [&](auto np) -> int {
+            constexpr int KK = decltype(k)::value, NW = decltype(w)::value, DEPTH = decltype(d)::value, EPI = decltype(e)::value, NP = decltype(np)::value;
+            if constexpr (DEPTH == 2 && (NW != 8 || NP != 3)) {
+              return SGC_EUNSUP;                                   // not reached: see depth above
+            } else {
+              static std::atomic<uint64_t> attr_done{0};           // one per kernel: a static of the generic lambda's instantiation
+              ensure_dynamic_lds((const void *)rows_gemm_bf16x3_kernel<KK, NW, DEPTH, EPI, NP>, rows_lds_bytes(KK), attr_done);
+              hipLaunchKernelGGL((rows_gemm_bf16x3_kernel<KK, NW, DEPTH, EPI, NP>), dim3(grid), dim3(NW * 64), rows_lds_bytes(KK), st, p);
+              return check_launch("rows_gemm_bf16x3_kernel");
+            }
+          });
+        });
+      });
+    });
   });
-}
-
-template <int K, int NW, int DEPTH>
-static int launch_rows_gemm(const RowsGemmParams &p, int grid, hipStream_t st) {
-  if (p.hm_cm > 0 && p.hm_bf16) return launch_rows_gemm_e<K, NW, DEPTH, 3>(p, grid, st);
-  if (p.hm_cm > 0) return launch_rows_gemm_e<K, NW, DEPTH, 1>(p, grid, st);
-  if (p.residual) return launch_rows_gemm_e<K, NW, DEPTH, 2>(p, grid, st);
-  return launch_rows_gemm_e<K, NW, DEPTH, 0>(p, grid, st);
 }
 
 // Can the persistent kernel take this GEMM?  K in {128, 256}; whole 128-column groups; 32-bit byte offsets into x and y;
@@ -590,25 +405,6 @@ bool rows_gemm_gather_supported(int K, int N, int64_t x_rows, int64_t rows) {
   return rows_gemm_supported(K, N, 0, 0, rows, K) && N == 128 && x_rows > 0 && (x_rows + 1) * K * 4 < (int64_t)RG_OOB;
 }
 
-template <int NP>
-static void launch_gather_pc(const RowsGemmParams &p, int grid, hipStream_t st) {
-  constexpr int smem = 2 * 2 * RG_ROWS * (256 + 8) * (int)sizeof(uint16_t);
-  static std::atomic<uint64_t> attr_done{0};
-  ensure_dynamic_lds((const void *)rows_gemm_gather_pc_kernel<256, NP>, smem, attr_done);
-  hipLaunchKernelGGL((rows_gemm_gather_pc_kernel<256, NP>), dim3(grid), dim3(512), smem, st, p);
-}
-
-template <int K>
-static int launch_rows_gemm_gather(const RowsGemmParams &p, int grid, hipStream_t st) {
-  constexpr int smem = 2 * 2 * RG_ROWS * (K + 8) * (int)sizeof(uint16_t);
-  with_products(g_conv_products, [&](auto np) {
-    static std::atomic<uint64_t> attr_done{0};             // one per NP: a static of the generic lambda's instantiation
-    ensure_dynamic_lds((const void *)rows_gemm_bf16x3_kernel<K, 4, 1, 0, np(), true>, smem, attr_done);
-    hipLaunchKernelGGL((rows_gemm_bf16x3_kernel<K, 4, 1, 0, np(), true>), dim3(grid), dim3(256), smem, st, p);
-  });
-  return check_launch("rows_gemm_bf16x3_kernel (gather)");
-}
-
 int rows_gemm_gather_launch(const float *x, int64_t x_rows, const float *gw, const int32_t *go, const uint16_t *w_hi, const uint16_t *w_lo,
                             const float *shift, float *y, const int32_t *m_dev, int M, int K, int N, hipStream_t st) {
   RowsGemmParams p = {};
@@ -616,21 +412,20 @@ int rows_gemm_gather_launch(const float *x, int64_t x_rows, const float *gw, con
   p.w_hi = reinterpret_cast<const __bf16 *>(w_hi); p.w_lo = reinterpret_cast<const __bf16 *>(w_lo);
   p.shift = shift; p.y = y; p.m_dev = m_dev; p.M = M; p.N = N;
   p.y_bytes = (int64_t)M * N * 4;
-  p.ncg = N / 128;
+  p.ncg = 1;                                                    // N == 128: one column group
   const int cap_tiles = ceil_div(M, RG_ROWS);
-  int stripes = device_cus() * 2 / p.ncg;                       // two 4-wave workgroups per CU
-  if (g_tune_rows_cu_pct > 0 && g_tune_rows_cu_pct < 100) stripes = stripes * g_tune_rows_cu_pct / 100;
-  if (stripes > cap_tiles) stripes = cap_tiles;
-  stripes = (stripes + 7) / 8 * 8;
-  const int grid = stripes * p.ncg;
-  if (K == 256) {
-    int s8 = device_cus();                                      // one 8-wave workgroup per CU
-    if (g_tune_rows_cu_pct > 0 && g_tune_rows_cu_pct < 100) s8 = s8 * g_tune_rows_cu_pct / 100;
-    if (s8 > cap_tiles) s8 = cap_tiles;
-    with_products(g_conv_products, [&](auto np) { launch_gather_pc<np()>(p, s8, st); });
-    return check_launch("rows_gemm_gather_pc_kernel");
-  }
-  return launch_rows_gemm_gather<128>(p, grid, st);
+  // K == 256: one 8-wave producer / consumer workgroup per CU; K == 128: two 4-wave workgroups of the lockstep kernel
+  return with_products(g_conv_products, [&](auto np) {
+    static std::atomic<uint64_t> attr_done[2];                  // per NP: statics of the generic lambda's instantiation
+    if (K == 256) {
+      ensure_dynamic_lds((const void *)rows_gemm_gather_pc_kernel<256, np()>, rows_lds_bytes(256), attr_done[0]);
+      hipLaunchKernelGGL((rows_gemm_gather_pc_kernel<256, np()>), dim3(persistent_stripes(cap_tiles, 1, 1)), dim3(512), rows_lds_bytes(256), st, p);
+      return check_launch("rows_gemm_gather_pc_kernel");
+    }
+    ensure_dynamic_lds((const void *)rows_gemm_bf16x3_kernel<128, 4, 1, 0, np(), true>, rows_lds_bytes(128), attr_done[1]);
+    hipLaunchKernelGGL((rows_gemm_bf16x3_kernel<128, 4, 1, 0, np(), true>), dim3(persistent_stripes(cap_tiles, 2, 1)), dim3(256), rows_lds_bytes(128), st, p);
+    return check_launch("rows_gemm_bf16x3_kernel (gather)");
+  });
 }
 
 int rows_gemm_launch(const float *x, int64_t ldx, const uint16_t *w_hi, const uint16_t *w_lo, const float *scale,
@@ -648,28 +443,10 @@ int rows_gemm_launch(const float *x, int64_t ldx, const uint16_t *w_hi, const ui
     static const bool diag_ok = getenv("SGC_DIAG") && atoi(getenv("SGC_DIAG")) == 1;
     p.diag = diag_ok ? g_tune_rows_diag : 0;
   }
-  RG_STAMP_BIND(p);
-  const int nw = (N % 256 == 0) ? 8 : 4;
+  const int nw = (N % 256 == 0) ? 8 : 4;                        // one 8-wave workgroup or two 4-wave workgroups per CU
   p.ncg = N / (nw * 32);
-  const int cap_tiles = ceil_div(M, RG_ROWS);
-  // one 8-wave workgroup or two 4-wave workgroups per CU; stripes are a multiple of 8 (the XCD-aware deal of the kernel)
-  const int per_cu = nw == 8 ? 1 : 2;
-  int stripes = device_cus() * per_cu / p.ncg;
-  if (g_tune_rows_cu_pct > 0 && g_tune_rows_cu_pct < 100) stripes = stripes * g_tune_rows_cu_pct / 100;   // leave CUs to the other streams
-  if (stripes > cap_tiles) stripes = cap_tiles;
-  stripes = (stripes + 7) / 8 * 8;
-  const int grid = stripes * p.ncg;
-  const int depth = nw == 8 ? g_tune_rows_depth : 1;
-  if (K == 256) {
-    if (nw == 8) return depth == 0 ? launch_rows_gemm<256, 8, 0>(p, grid, st) : depth == 2 ? launch_rows_gemm<256, 8, 2>(p, grid, st) : launch_rows_gemm<256, 8, 1>(p, grid, st);
-    return launch_rows_gemm<256, 4, 1>(p, grid, st);
-  }
-  if (nw == 8) return depth == 0 ? launch_rows_gemm<128, 8, 0>(p, grid, st) : depth == 2 ? launch_rows_gemm<128, 8, 2>(p, grid, st) : launch_rows_gemm<128, 8, 1>(p, grid, st);
-  return launch_rows_gemm<128, 4, 1>(p, grid, st);
+  const int stripes = persistent_stripes(ceil_div(M, RG_ROWS), nw == 8 ? 1 : 2, p.ncg);
+  return launch_rows_gemm(p, K, nw, stripes * p.ncg, st);
 }
 
 }  // namespace sgc
-
-#if defined(SGC_RG_STAMPS)
-extern "C" void sgc_diag_rows_stamp_buffer(unsigned long long *buf) { sgc::g_rows_stamp_buf = buf; }
-#endif

@@ -25,7 +25,7 @@
   X("rows_gemm", g_tune_rows_gemm, 1, "0: every row GEMM on the tile implicit-GEMM kernel")                                  \
   X("rows_diag", g_tune_rows_diag, 0, "timing experiments only (bit 0 no stores, 1 no loads, 2 no MFMA); needs SGC_DIAG=1")  \
   X("rows_cu_pct", g_tune_rows_cu_pct, 100, "persistent row GEMM: share of the CUs it occupies")                             \
-  X("rows_depth", g_tune_rows_depth, 1, "8-wave form: 1 / 2 tiles in flight ahead (lockstep), 0 staggered halves")           \
+  X("rows_depth", g_tune_rows_depth, 1, "8-wave form: 2 = two tiles in flight ahead, anything else = one")                   \
   /* convolution plan (conv3d.hip: plan_conv and its helpers) */                                                              \
   X("conv_halo", g_tune_conv_halo, 1, "3x3x3 stride-1 layers: 0 tile kernel, 1 halo-resident kernel")                        \
   X("halo_min_cout", g_tune_halo_min_cout, 16, "fewest output channels for the halo kernel")                                 \

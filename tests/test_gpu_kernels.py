@@ -665,14 +665,8 @@ def test_bf16_storage_mode_of_the_tiled_gather(C, HW, bins, oracle_ops, gpu_ops)
     assert torch.equal(y16, y32.to(torch.bfloat16))
 
 
-@pytest.mark.parametrize("C", [128, 256])
-@pytest.mark.parametrize("HW,stride_extra", [((29, 40), 0), ((15, 20), 0), ((14, 20), 20)])
-def test_geometry_sample_fused_with_its_linear(HW, stride_extra, C, oracle_ops, gpu_ops):
-    """sgc_pairs_geometry_linear_bf16x3 (round 6): the geometry-aware sample of every visible pair built while the row GEMM stages
-    its tile == sgc_pairs_geometry_sample + sgc_linear_rows_bf16x3, BIT FOR BIT (same fmas, same GEMM kernel), host-counted and
-    device-counted, with the cropped-row camera stride; and within the bf16x3 bound of the oracle's two steps.  C = 128: the gather
-    form of the persistent row GEMM; C = 256: its producer / consumer form (rows_gemm_gather_pc_kernel)."""
-    N, Nq, D, Cout = 5, 800, 12, 128
+def _geometry_linear_case(HW, stride_extra, C, oracle_ops, N=5, Nq=800, D=12, Cout=128):
+    """The scene of the fused geometry sample + Linear tests: maps, depth distribution, projected points, pair list, weight, bias."""
     H, W = HW
     S = H * W + stride_extra
     ref3d, origin, proj = _scene(N, Nq, 13)
@@ -684,6 +678,20 @@ def test_geometry_sample_fused_with_its_linear(HW, stride_extra, C, oracle_ops, 
     dist = torch.randn(N, S, D, generator=g).mul(2).softmax(-1).contiguous()
     w = torch.randn(1, Cout, C, generator=g) * 0.1
     b = torch.randn(Cout, generator=g)
+    return feat, dist, rc, pc, n, w, b
+
+
+@pytest.mark.parametrize("C", [128, 256])
+@pytest.mark.parametrize("HW,stride_extra", [((29, 40), 0), ((15, 20), 0), ((14, 20), 20)])
+def test_geometry_sample_fused_with_its_linear(HW, stride_extra, C, oracle_ops, gpu_ops):
+    """sgc_pairs_geometry_linear_bf16x3 (round 6): the geometry-aware sample of every visible pair built while the row GEMM stages
+    its tile == sgc_pairs_geometry_sample + sgc_linear_rows_bf16x3, BIT FOR BIT (same fmas, same GEMM kernel), host-counted and
+    device-counted, with the cropped-row camera stride; and within the bf16x3 bound of the oracle's two steps.  C = 128: the gather
+    form of the persistent row GEMM; C = 256: its producer / consumer form (rows_gemm_gather_pc_kernel)."""
+    N, Cout = 5, 128
+    H, W = HW
+    S = H * W + stride_extra
+    feat, dist, rc, pc, n, w, b = _geometry_linear_case(HW, stride_extra, C, oracle_ops)
     hi, lo = gpu_ops.split_bf16(w)
     cu = lambda t: t.cuda()
     gpc = {k: cu(v) for k, v in pc.items()}
@@ -965,11 +973,114 @@ def test_persistent_row_gemm_head_major_and_epilogues(N, S, cin, M, oracle_ops, 
         assert torch.equal(y, y_tile), (relu, r is not None)
 
 
-@pytest.mark.parametrize("Nq,C,seen", [(400, 256, 0.7), (6401, 256, 0.95), (33, 256, 0.0), (1000, 128, 0.6), (31, 128, 1.0)])
-def test_level_tail_equals_the_six_launches_it_replaces(Nq, C, seen, oracle_ops, gpu_ops):
-    """sgc_level_tail (out_proj on the seen voxels + zero rows elsewhere -> LayerNorm -> FFN with identity -> LayerNorm in one
-    launch; reference: TU/deformable_cross_attention.py:826-837, TU/encoder.py:311-338, mmcv FFN) against (a) the CPU
-    oracle's composition, 1e-4 of the scale, and (b) the separate HIP launches it replaces -- bit for bit."""
+@pytest.mark.parametrize("cin", [128, 256])
+def test_persistent_row_gemm_when_a_workgroup_owns_many_tiles(cin, oracle_ops, gpu_ops):
+    """The tile loops of the persistent kernel past their peeled first iterations: with rows_cu_pct = 25 an 8-wave launch has 64
+    stripes on a 256-CU device, and 10001 rows are 313 tiles -- 4 or 5 per workgroup, both parities of the two-tiles-ahead form
+    (even / odd / pair loop / odd tail) and several turns of the one-ahead loop.  Every geometry gives the bits of the default
+    launch (one tile per workgroup here would not show a wrong buffer or register set), within the bf16x3 bound of the oracle;
+    a device count leaves the rows past it untouched."""
+    rows, cout = 10001, 256
+    g = torch.Generator().manual_seed(rows + cin)
+    x = torch.randn(rows, cin, generator=g)
+    w = torch.randn(cout, cin, generator=g) * 0.1
+    b = torch.randn(cout, generator=g)
+    hi, lo = gpu_ops.split_bf16(w.view(1, cout, cin))
+    xc, hc, lc, bc = x.cuda(), hi.cuda(), lo.cuda(), b.cuda()
+    want = oracle_ops.linear_rows_bf16x3(x, hi, lo, b)
+    y0 = gpu_ops.linear_rows_bf16x3(xc, hc, lc, bc)
+    cnt = (rows * 2) // 3
+    cnt_dev = torch.tensor([cnt], dtype=torch.int32, device="cuda")
+    try:
+        gpu_ops.lib.call("sgc_set_tuning", b"rows_cu_pct", 25)
+        for depth in (1, 2):
+            gpu_ops.lib.call("sgc_set_tuning", b"rows_depth", depth)
+            y = gpu_ops.linear_rows_bf16x3(xc, hc, lc, bc)
+            assert torch.equal(y, y0), depth
+            close(y, want, tol=1e-4)
+            out = torch.full((rows, cout), 7.0, device="cuda")
+            gpu_ops.linear_rows_bf16x3(xc, hc, lc, bc, count=cnt_dev, out=out)
+            assert torch.equal(out[:cnt], y0[:cnt]) and bool((out[cnt:] == 7.0).all()), depth
+    finally:
+        gpu_ops.lib.call("sgc_set_tuning", b"rows_cu_pct", 100)
+        gpu_ops.lib.call("sgc_set_tuning", b"rows_depth", 1)
+
+
+def test_row_kernels_in_the_one_product_modes(oracle_ops, gpu_ops):
+    """sgc_set_conv_products 1 / 2 (plain bf16 / plain fp16 products) on the weight-stationary row kernels beyond the 8-wave K = 256
+    plain epilogue that tests/test_gpu_conv3d.py covers: the 4-wave forms, K = 128, the head-major and residual epilogues, both
+    gather kernels and the level tail.  In each mode, with the weights split for it: the row GEMM equals the tile kernel bit for
+    bit and meets the oracle in the same mode within 1e-5 of the scale (the bound of test_plain_bf16_mode_...: same operands, fp32
+    sums in another order); head-major == the permuted rows; fused gather == sample + Linear; level tail == the six launches."""
+    cu = lambda t: t.cuda() if isinstance(t, torch.Tensor) else t      # noqa: E731
+    cup = lambda pr: tuple(cu(t) for t in pr)                          # noqa: E731
+
+    def on_tile_kernel(fn):
+        try:
+            gpu_ops.lib.call("sgc_set_tuning", b"rows_gemm", 0)
+            return fn()
+        finally:
+            gpu_ops.lib.call("sgc_set_tuning", b"rows_gemm", 1)
+
+    try:
+        for mode in (1, 2):
+            for ops in (gpu_ops, oracle_ops):
+                ops.lib.call("sgc_set_conv_products", mode)
+            g = torch.Generator().manual_seed(40 + mode)
+            # plain row GEMM: 4 waves at K = 128 and at K = 256
+            for rows, cin, cout in ((77, 128, 128), (333, 256, 128)):
+                x = torch.randn(rows, cin, generator=g)
+                w = torch.randn(1, cout, cin, generator=g) * 0.1
+                b = torch.randn(cout, generator=g)
+                hi, lo = gpu_ops.split_operand(w)
+                y = gpu_ops.linear_rows_bf16x3(cu(x), cu(hi), cu(lo), cu(b))
+                assert torch.equal(y, on_tile_kernel(lambda: gpu_ops.linear_rows_bf16x3(cu(x), cu(hi), cu(lo), cu(b)))), (mode, rows)
+                ref = oracle_ops.linear_rows_bf16x3(x, hi, lo, b)
+                err = float((y.cpu() - ref).abs().max())
+                assert err <= 1e-5 * max(1.0, float(ref.abs().max())), (mode, rows, err)
+            # head-major stores, fp32 and bf16
+            N, S, C, M = 3, 47, 128, 8
+            x = torch.randn(N * S, C, generator=g)
+            w = torch.randn(1, C, C, generator=g) * 0.1
+            b = torch.randn(C, generator=g)
+            hi, lo = gpu_ops.split_operand(w)
+            rows_y = gpu_ops.linear_rows_bf16x3(cu(x), cu(hi), cu(lo), cu(b))
+            for dt in (torch.float32, torch.bfloat16):
+                y = gpu_ops.linear_rows_headmajor_bf16x3(cu(x), cu(hi), cu(lo), cu(b), N, S, M, out_dtype=dt)
+                assert torch.equal(y, rows_y.view(N, S, M, C // M).permute(0, 2, 1, 3).contiguous().to(dt)), (mode, dt)
+            # residual epilogue, both relu orders
+            rows, C = 95, 128
+            x = torch.randn(rows, C, generator=g)
+            w = torch.randn(1, C, C, generator=g) * 0.1
+            sc, b, res = torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g), torch.randn(rows, C, generator=g)
+            hi, lo = gpu_ops.split_operand(w)
+            for relu in (1, 2):
+                conv = lambda: gpu_ops.conv3d_cl_bf16x3(cu(x), cu(hi), cu(lo), (rows, 1, 1), 1, 1, False, cu(sc), cu(b), cu(res), relu)[0]   # noqa: E731
+                assert torch.equal(conv(), on_tile_kernel(conv)), (mode, relu)
+            # fused gather: the lockstep gather form (C = 128) and the producer / consumer form (C = 256)
+            for C in (128, 256):
+                H, W = 15, 20
+                feat, dist, rc, pc, n, w, b = _geometry_linear_case((H, W), 0, C, oracle_ops)
+                hi, lo = gpu_ops.split_operand(w)
+                gpc = {k: cu(v) for k, v in pc.items()}
+                geo = gpu_ops.pairs_geometry_sample(cu(feat), cu(dist), cu(rc), gpc["pair_cam"], gpc["pair_q"], n, H, W)
+                two = gpu_ops.linear_rows_bf16x3(geo, cu(hi), cu(lo), cu(b))
+                one = gpu_ops.pairs_geometry_linear(cu(feat), cu(dist), cu(rc), gpc["pair_cam"], gpc["pair_q"], n, H, W, cu(hi), cu(lo), cu(b))
+                assert one.shape == two.shape and torch.equal(one, two), (mode, C)
+            # level tail
+            for Nq, C, seen in ((33, 128, 0.6), (65, 256, 0.7)):
+                ctx, row_of, vis, (wo, w1, w2), (bo, b1, b2), ln1, ln2 = _level_tail_case(Nq, C, seen)
+                sp = lambda w: gpu_ops.split_operand(w.view(1, *w.shape))       # noqa: E731
+                so, s1, s2 = sp(wo), sp(w1), sp(w2)
+                y = gpu_ops.level_tail(cu(ctx), cu(row_of), cup(so), cu(bo), cup(ln1), cup(s1), cu(b1), cup(s2), cu(b2), cup(ln2))
+                assert torch.equal(y, _level_tail_six_launches(gpu_ops, ctx, row_of, vis, so, bo, ln1, s1, b1, s2, b2, ln2)), (mode, C)
+    finally:
+        for ops in (gpu_ops, oracle_ops):
+            ops.lib.call("sgc_set_conv_products", 3)
+
+
+def _level_tail_case(Nq, C, seen):
+    """Inputs of a VoxFormer level tail: compact ctx rows, the voxel -> row map, the three fp32 weights, biases, LayerNorms."""
     F = 2 * C
     g = torch.Generator().manual_seed(Nq + C)
     vis = torch.rand(Nq, generator=g) < seen
@@ -982,14 +1093,13 @@ def test_level_tail_equals_the_six_launches_it_replaces(Nq, C, seen, oracle_ops,
     bo, b1, b2 = torch.randn(C, generator=g) * 0.1, torch.randn(F, generator=g) * 0.1, torch.randn(C, generator=g) * 0.1
     ln1 = (torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g) * 0.1, 1e-5)
     ln2 = (torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g) * 0.1, 1e-5)
-    sp = lambda w: gpu_ops.split_bf16(w.view(1, *w.shape))             # noqa: E731
-    so, s1, s2 = sp(wo), sp(w1), sp(w2)
+    return ctx, row_of, vis, (wo, w1, w2), (bo, b1, b2), ln1, ln2
+
+
+def _level_tail_six_launches(gpu_ops, ctx, row_of, vis, so, bo, ln1, s1, b1, s2, b2, ln2):
+    """What sgc_level_tail replaces: row GEMM, scatter, LayerNorm, two 1x1x1 GEMMs, LayerNorm -- as separate HIP launches."""
+    Nq, C = row_of.numel(), ctx.shape[1]
     cu = lambda t: t.cuda() if isinstance(t, torch.Tensor) else t      # noqa: E731
-    cup = lambda pr: tuple(cu(t) for t in pr)                          # noqa: E731
-    y = gpu_ops.level_tail(cu(ctx), cu(row_of), cup(so), cu(bo), cup(ln1), cup(s1), cu(b1), cup(s2), cu(b2), cup(ln2))
-    y_o = oracle_ops.level_tail(ctx, row_of, so, bo, ln1, s1, b1, s2, b2, ln2)
-    close(y, y_o, tol=1e-4)
-    # the six launches
     valid_index = torch.nonzero(vis).view(-1).to(torch.int32).cuda()
     x0 = torch.zeros(Nq, C, device="cuda")
     if int(vis.sum()):
@@ -998,8 +1108,23 @@ def test_level_tail_equals_the_six_launches_it_replaces(Nq, C, seen, oracle_ops,
     x1 = gpu_ops.layer_norm_rows(x0, cu(ln1[0]), cu(ln1[1]), ln1[2])
     h, _ = gpu_ops.conv3d_cl_bf16x3(x1, s1[0].cuda(), s1[1].cuda(), (Nq, 1, 1), 1, 1, False, None, cu(b1), None, 2)
     x2, _ = gpu_ops.conv3d_cl_bf16x3(h, s2[0].cuda(), s2[1].cuda(), (Nq, 1, 1), 1, 1, False, None, cu(b2), x1, 0)
-    want = gpu_ops.layer_norm_rows(x2, cu(ln2[0]), cu(ln2[1]), ln2[2])
-    assert torch.equal(y, want)
+    return gpu_ops.layer_norm_rows(x2, cu(ln2[0]), cu(ln2[1]), ln2[2])
+
+
+@pytest.mark.parametrize("Nq,C,seen", [(400, 256, 0.7), (6401, 256, 0.95), (33, 256, 0.0), (1000, 128, 0.6), (31, 128, 1.0)])
+def test_level_tail_equals_the_six_launches_it_replaces(Nq, C, seen, oracle_ops, gpu_ops):
+    """sgc_level_tail (out_proj on the seen voxels + zero rows elsewhere -> LayerNorm -> FFN with identity -> LayerNorm in one
+    launch; reference: TU/deformable_cross_attention.py:826-837, TU/encoder.py:311-338, mmcv FFN) against (a) the CPU
+    oracle's composition, 1e-4 of the scale, and (b) the separate HIP launches it replaces -- bit for bit."""
+    ctx, row_of, vis, (wo, w1, w2), (bo, b1, b2), ln1, ln2 = _level_tail_case(Nq, C, seen)
+    sp = lambda w: gpu_ops.split_bf16(w.view(1, *w.shape))             # noqa: E731
+    so, s1, s2 = sp(wo), sp(w1), sp(w2)
+    cu = lambda t: t.cuda() if isinstance(t, torch.Tensor) else t      # noqa: E731
+    cup = lambda pr: tuple(cu(t) for t in pr)                          # noqa: E731
+    y = gpu_ops.level_tail(cu(ctx), cu(row_of), cup(so), cu(bo), cup(ln1), cup(s1), cu(b1), cup(s2), cu(b2), cup(ln2))
+    y_o = oracle_ops.level_tail(ctx, row_of, so, bo, ln1, s1, b1, s2, b2, ln2)
+    close(y, y_o, tol=1e-4)
+    assert torch.equal(y, _level_tail_six_launches(gpu_ops, ctx, row_of, vis, so, bo, ln1, s1, b1, s2, b2, ln2))
 
 
 @pytest.mark.timeout(1200)
