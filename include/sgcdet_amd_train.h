@@ -156,6 +156,35 @@ int sgc_head_loss_scale_grads(const float *grads, float *out, const int64_t *lev
                               const void *workspace, const float *grad_centerness, const float *grad_bbox, const float *grad_cls,
                               sgc_stream_t stream);
 
+/* ------------------------------------------------------------------------- *
+ * 12. Training the image backbone: the 2-D weight gradient and the backward of the frozen-norm epilogue
+ *     (csrc/conv3d_wgrad.hip, csrc/frozen_norm.hip)
+ * ------------------------------------------------------------------------- */
+
+/* Weight gradient of nn.Conv2d(k, stride, padding = k / 2) over channels-last rows:
+ *   dw[kh*k + kw][co][ci] = sum over (n, oh, ow) of dy[(n,oh,ow)][co] * x[(n, oh*s + kh - k/2, ow*s + kw - k/2)][ci]
+ *   x [N*H*W, Cin], dy [N*OH*OW, Cout], OH = ceil(H / s), OW = ceil(W / s), dw [k*k, Cout, Cin] fully written
+ *   (the layout sgc_unpack_conv_wgrad turns into the parameter's); a tap outside its image adds nothing.
+ *   k in {1, 3}, s in {1, 2}, any H, W >= 1, Cin % 4 == 0, Cout % 4 == 0, 16-byte aligned pointers.
+ * The tile kernel of sgc_conv3d_wgrad_bf16x3 with a reduction row decoded as (image, h, w): bf16x3 products (always three,
+ * whatever sgc_set_conv_products says), fp32 accumulation, the reduction rows split over workgroups.  With a workspace of
+ * sgc_conv2d_wgrad_workspace_floats(...) floats the partial sums are added in a fixed order (bit-identical run to run); without
+ * one (null, or too small) one workgroup per tile walks the whole range.  The query returns 0 for a shape that is not split and
+ * -1 for one the entry refuses.  SGC_EUNSUP for other k / s / channel counts, and for x or dy of 4 GiB or more. */
+int sgc_conv2d_wgrad_bf16x3(const float *x, const float *dy, float *dw, int N, int H, int W, int Cin, int Cout, int ksize,
+                            int stride, float *workspace_or_null, int64_t workspace_floats, sgc_stream_t stream);
+int64_t sgc_conv2d_wgrad_workspace_floats(int N, int H, int W, int Cin, int Cout, int ksize, int stride);
+
+/* Backward of the epilogue y = act(conv * scale + shift [+ residual]) of a layer whose norm is frozen, one pass over dy and y:
+ *   gate       = relu ? (y[r][c] > 0) : 1
+ *   g[r][c]    = gate ? dy[r][c] * scale[c] : 0      (scale null: 1)  -- feeds the input and weight gradients
+ *   gres[r][c] = gate ? dy[r][c] : 0                 (gres null: not written) -- the residual's gradient when the ReLU sits behind the add
+ * dy, y, g, gres [rows, C] dense;  y may be null with relu = 0.  The gate is a select: a NaN of dy goes through where the gate is
+ * open and is dropped where it is closed; the product is a single fp32 multiply.  Needs C % 4 == 0 and 16-byte aligned pointers
+ * (SGC_EUNSUP otherwise). */
+int sgc_frozen_norm_act_backward(const float *dy, const float *y_or_null, const float *scale_or_null, float *g, float *gres_or_null,
+                                 int64_t rows, int C, int relu, sgc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

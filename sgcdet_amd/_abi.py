@@ -109,12 +109,15 @@ TRAIN_SIGNATURES = {
     "sgc_head_loss_forward": [_p, _i] + [_p] * 4 + [_i] * 4 + [_d] * 5 + [_p] * 5 + [C.c_int64, _p],      # levels: HOST array of sgc_head_loss_level
     "sgc_head_loss_finalize": [_p, C.c_int64, _p, _i, _p] + [_d] * 3 + [_p] * 3,                         # level_points: HOST int64 array
     "sgc_head_loss_scale_grads": [_p, _p, _p] + [_i] * 3 + [_p] * 5,
+    "sgc_conv2d_wgrad_bf16x3": [_p] * 3 + [_i] * 7 + [_p, C.c_int64] + [_p],
+    "sgc_frozen_norm_act_backward": [_p] * 5 + [C.c_int64, _i, _i] + [_p],
 }
 
 TRAIN_INTROSPECTION = {
     "sgc_plane_sweep_corr_backward_workspace_bytes": (C.c_int64, [_i] * 5),
     "sgc_grad_sqnorm_batch_workspace_bytes": (C.c_int64, [_i]),
     "sgc_head_loss_workspace_bytes": (C.c_int64, [_i] * 2),
+    "sgc_conv2d_wgrad_workspace_floats": (C.c_int64, [_i] * 7),
 }
 
 # include/sgcdet_amd_image.h: the 2-D convolutions of the image-side CNNs (no CPU-oracle twin)

@@ -1,4 +1,5 @@
-// Weight gradient of the implicit-GEMM convolutions (training): the tile kernel, the two halo forms, their reduction and entry points.
+// Weight gradient of the implicit-GEMM convolutions (training): the tile kernel (3-D, and 2-D over image rows by an addressing policy), the two
+// halo forms of the 3-D entry, their reduction and the entry points.
 #include "conv_common.hpp"
 #include "mma.hpp"
 #include "diag.hpp"
@@ -30,7 +31,10 @@ struct WgradParams {
 // WM = 2: 4 waves (2 x 2, 64 x 64 each), every thread stages one block of BOTH operands; WM = 4: 8 waves (4 x 2, 32 x 64 each),
 // threads 0-255 stage the dy tile and 256-511 the x tile (half the loads, conversions and registers per thread, twice the
 // waves to hide them).
-template <int WM>
+// IMG: the 2-D form (sgc_conv2d_wgrad_bf16x3).  A reduction row decodes as (image, h, w) = (x, y, z) of the carried coordinates,
+// the taps are the k * k taps of (y, z) only and the leading coordinate is neither strided nor padded -- it picks the image, so
+// no tap crosses one.  Staging, MMA and store are the 3-D kernel's.
+template <int WM, bool IMG = false>
 __global__ __launch_bounds__(WM * 128) void conv3d_wgrad_bf16x3_kernel(const WgradParams p) {
   constexpr int TMW = 4 / WM * 1;                           // 32-row tiles per wave along M: 2 (WM = 2) or 1 (WM = 4)
   constexpr int BMW = 128, BNW = 128;
@@ -43,7 +47,7 @@ __global__ __launch_bounds__(WM * 128) void conv3d_wgrad_bf16x3_kernel(const Wgr
   const int tap = blockIdx.z % p.taps, split = blockIdx.z / p.taps;
   const int s_lo = split * p.steps_per_split, s_hi = min(p.ksteps, s_lo + p.steps_per_split);
   int dx = 0, dy_ = 0, dz = 0;
-  if (p.ksize > 1) { dx = tap / (p.ksize * p.ksize); dy_ = (tap / p.ksize) % p.ksize; dz = tap % p.ksize; }
+  if (p.ksize > 1) { dx = IMG ? 0 : tap / (p.ksize * p.ksize); dy_ = (tap / p.ksize) % p.ksize; dz = tap % p.ksize; }
 
   const int role = WM == 4 ? __builtin_amdgcn_readfirstlane(tid >> 8) : 2;   // 0: stages dy, 1: stages x, 2: both (wave-uniform)
   const int kb = tid & 7, cb = (tid & 255) >> 3;            // this thread's block: voxels 4 kb .. + 3 of the step, channels 4 cb .. + 3
@@ -75,7 +79,7 @@ __global__ __launch_bounds__(WM * 128) void conv3d_wgrad_bf16x3_kernel(const Wgr
         ra[j] = make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
       }
       if (role != 0) {
-        const int xx = vx[j] * p.stride + dx - p.pad, yy = vy[j] * p.stride + dy_ - p.pad, zz = vz[j] * p.stride + dz - p.pad;
+        const int xx = IMG ? vx[j] : vx[j] * p.stride + dx - p.pad, yy = vy[j] * p.stride + dy_ - p.pad, zz = vz[j] * p.stride + dz - p.pad;
         const bool in = live && b_ok && xx >= 0 && xx < p.ix && yy >= 0 && yy < p.iy && zz >= 0 && zz < p.iz;
         const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(
             xr, in ? ((unsigned)((xx * p.iy + yy) * p.iz + zz) * (unsigned)p.Cin + ci0 + 4 * cb) * 4u : OOB, 0, 0);
@@ -643,6 +647,25 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float4 *__restr
   }
 }
 
+// Reduction rows, K steps, split count and the carried-coordinate digits of a geometry whose (ox, oy, oz), taps and channel counts are set.
+static int wgrad_split_plan(WgradParams &p, const char *who) {
+  const int Cin = p.Cin, Cout = p.Cout;
+  p.OV = p.ox * p.oy * p.oz;
+  p.ksteps = ceil_div(p.OV, 32);
+  const int tiles = ceil_div(Cout, 128) * ceil_div(Cin, 128) * p.taps;
+  int splits = 1;
+  while (tiles * splits < 512 && p.ksteps / (splits * 2) >= 16) splits *= 2;     // fill the chip twice over; >= 16 K-steps per split
+  // a layer that still leaves most CUs idle (the nn.Linear layers of a level: 800 rows, 4 tiles) is bound by the load latency
+  // of its serial K-steps (~2.5 us each), not by flops: spread the steps over idle CUs, down to 3 per workgroup
+  while (tiles * splits < 256 && p.ksteps / (splits * 2) >= 3) splits *= 2;
+  p.steps_per_split = ceil_div(p.ksteps, splits);
+  p.splits = ceil_div(p.ksteps, p.steps_per_split);
+  p.ax = 32 / (p.oy * p.oz); p.by = (32 % (p.oy * p.oz)) / p.oz; p.cz = 32 % p.oz;
+  if ((int64_t)p.OV * Cout * 4 >= 0xfffffff0ll - 65536 || (int64_t)p.ix * p.iy * p.iz * Cin * 4 >= 0xfffffff0ll - 65536)
+    return set_error(SGC_EUNSUP, "%s: x and dy must stay below 4 GiB each", who);
+  return SGC_OK;
+}
+
 static int wgrad_geometry(WgradParams &p, int ix, int iy, int iz, int Cin, int Cout, int ksize, int stride) {
   if (Cin <= 0 || Cout <= 0 || ix <= 0 || iy <= 0 || iz <= 0) return set_error(SGC_EINVAL, "sgc_conv3d_wgrad_bf16x3: bad size");
   if ((Cin & 3) || (Cout & 3)) return set_error(SGC_EUNSUP, "sgc_conv3d_wgrad_bf16x3: Cin and Cout must be multiples of 4");
@@ -657,20 +680,53 @@ static int wgrad_geometry(WgradParams &p, int ix, int iy, int iz, int Cin, int C
   p.Cin = Cin; p.Cout = Cout; p.ix = ix; p.iy = iy; p.iz = iz; p.ksize = ksize; p.stride = stride;
   p.taps = ksize * ksize * ksize;
   p.ox = (ix + 2 * p.pad - ksize) / stride + 1; p.oy = (iy + 2 * p.pad - ksize) / stride + 1; p.oz = (iz + 2 * p.pad - ksize) / stride + 1;
-  p.OV = p.ox * p.oy * p.oz;
-  p.ksteps = ceil_div(p.OV, 32);
-  const int tiles = ceil_div(Cout, 128) * ceil_div(Cin, 128) * p.taps;
-  int splits = 1;
-  while (tiles * splits < 512 && p.ksteps / (splits * 2) >= 16) splits *= 2;     // fill the chip twice over; >= 16 K-steps per split
-  // a layer that still leaves most CUs idle (the nn.Linear layers of a level: 800 rows, 4 tiles) is bound by the load latency
-  // of its serial K-steps (~2.5 us each), not by flops: spread the steps over idle CUs, down to 3 per workgroup
-  while (tiles * splits < 256 && p.ksteps / (splits * 2) >= 3) splits *= 2;
-  p.steps_per_split = ceil_div(p.ksteps, splits);
-  p.splits = ceil_div(p.ksteps, p.steps_per_split);
-  p.ax = 32 / (p.oy * p.oz); p.by = (32 % (p.oy * p.oz)) / p.oz; p.cz = 32 % p.oz;
-  if ((int64_t)p.OV * Cout * 4 >= 0xfffffff0ll - 65536 || (int64_t)ix * iy * iz * Cin * 4 >= 0xfffffff0ll - 65536)
-    return set_error(SGC_EUNSUP, "sgc_conv3d_wgrad_bf16x3: x and dy must stay below 4 GiB each");
-  return SGC_OK;
+  return wgrad_split_plan(p, "sgc_conv3d_wgrad_bf16x3");
+}
+
+// The 2-D form: (ix, iy, iz) = (N, H, W), the image index takes no part in the window (see the kernel's IMG policy).
+static int wgrad2d_geometry(WgradParams &p, int N, int H, int W, int Cin, int Cout, int ksize, int stride) {
+  if (Cin <= 0 || Cout <= 0 || N <= 0 || H <= 0 || W <= 0) return set_error(SGC_EINVAL, "sgc_conv2d_wgrad_bf16x3: bad size");
+  if ((Cin & 3) || (Cout & 3)) return set_error(SGC_EUNSUP, "sgc_conv2d_wgrad_bf16x3: Cin and Cout must be multiples of 4");
+  if ((ksize != 1 && ksize != 3) || (stride != 1 && stride != 2))
+    return set_error(SGC_EUNSUP, "sgc_conv2d_wgrad_bf16x3: ksize in {1,3}, stride in {1,2}");
+  if ((int64_t)N * H * W >= ((int64_t)1 << 30)) return set_error(SGC_EUNSUP, "sgc_conv2d_wgrad_bf16x3: too many rows");
+  p.pad = ksize / 2;
+  p.Cin = Cin; p.Cout = Cout; p.ix = N; p.iy = H; p.iz = W; p.ksize = ksize; p.stride = stride;
+  p.taps = ksize * ksize;
+  p.ox = N; p.oy = (H + 2 * p.pad - ksize) / stride + 1; p.oz = (W + 2 * p.pad - ksize) / stride + 1;      // ceil(H / s), ceil(W / s)
+  return wgrad_split_plan(p, "sgc_conv2d_wgrad_bf16x3");
+}
+
+// The tile kernel (and the fixed-order reduction behind a split) on a prepared geometry: shared by the 3-D and the 2-D entry.
+template <bool IMG>
+static int wgrad_tile_launch(WgradParams &p, const float *x, const float *dy, float *dw, float *workspace_or_null, int64_t workspace_floats,
+                             sgc_stream_t stream) {
+  p.x = x; p.dy = dy;
+  const int64_t n = (int64_t)p.taps * p.Cout * p.Cin;
+  if (p.splits > 1 && !(workspace_or_null && workspace_floats >= p.splits * n)) {     // no workspace: one split (slower, same result class)
+    p.splits = 1;
+    p.steps_per_split = p.ksteps;
+  }
+  p.out = p.splits > 1 ? workspace_or_null : dw;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t smem = (size_t)2 * 4 * 128 * LDKH * sizeof(uint16_t);
+  static std::atomic<uint64_t> attr_done{0};
+  static std::atomic<uint64_t> attr_done8{0};
+  ensure_dynamic_lds((const void *)conv3d_wgrad_bf16x3_kernel<2, IMG>, (int)smem, attr_done);
+  ensure_dynamic_lds((const void *)conv3d_wgrad_bf16x3_kernel<4, IMG>, (int)smem, attr_done8);
+  const dim3 wgrid(ceil_div(p.Cout, 128), ceil_div(p.Cin, 128), p.taps * p.splits);
+  if (g_tune_wgrad_waves == 8) hipLaunchKernelGGL((conv3d_wgrad_bf16x3_kernel<4, IMG>), wgrid, dim3(512), smem, st, p);
+  else hipLaunchKernelGGL((conv3d_wgrad_bf16x3_kernel<2, IMG>), wgrid, dim3(256), smem, st, p);
+  int rc = check_launch("conv3d_wgrad_bf16x3_kernel");
+  if (rc) return rc;
+  if (p.splits > 1) {
+    const int64_t n4 = n / 4;
+    const int g = (int)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096);
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(g), dim3(256), 0, st, reinterpret_cast<const float4 *>(workspace_or_null),
+                       reinterpret_cast<float4 *>(dw), n4, p.splits);
+    rc = check_launch("wgrad_reduce_kernel");
+  }
+  return rc;
 }
 
 extern "C" int64_t sgc_conv3d_wgrad_workspace_floats(int ix, int iy, int iz, int Cin, int Cout, int ksize, int stride) {
@@ -732,30 +788,22 @@ extern "C" int sgc_conv3d_wgrad_bf16x3(const float *x, const float *dy, float *d
   WgradParams p = {};
   int rc = wgrad_geometry(p, ix, iy, iz, Cin, Cout, ksize, stride);
   if (rc) return rc;
-  p.x = x; p.dy = dy;
-  const int64_t n = (int64_t)p.taps * Cout * Cin;
-  if (p.splits > 1 && !(workspace_or_null && workspace_floats >= p.splits * n)) {     // no workspace: one split (slower, same result class)
-    p.splits = 1;
-    p.steps_per_split = p.ksteps;
-  }
-  p.out = p.splits > 1 ? workspace_or_null : dw;
-  hipStream_t st = (hipStream_t)stream;
-  const size_t smem = (size_t)2 * 4 * 128 * LDKH * sizeof(uint16_t);
-  static std::atomic<uint64_t> attr_done{0};
-  static std::atomic<uint64_t> attr_done8{0};
-  ensure_dynamic_lds((const void *)conv3d_wgrad_bf16x3_kernel<2>, (int)smem, attr_done);
-  ensure_dynamic_lds((const void *)conv3d_wgrad_bf16x3_kernel<4>, (int)smem, attr_done8);
-  const dim3 wgrid(ceil_div(Cout, 128), ceil_div(Cin, 128), p.taps * p.splits);
-  if (g_tune_wgrad_waves == 8) hipLaunchKernelGGL(conv3d_wgrad_bf16x3_kernel<4>, wgrid, dim3(512), smem, st, p);
-  else hipLaunchKernelGGL(conv3d_wgrad_bf16x3_kernel<2>, wgrid, dim3(256), smem, st, p);
-  rc = check_launch("conv3d_wgrad_bf16x3_kernel");
+  return wgrad_tile_launch<false>(p, x, dy, dw, workspace_or_null, workspace_floats, stream);
+}
+
+extern "C" int64_t sgc_conv2d_wgrad_workspace_floats(int N, int H, int W, int Cin, int Cout, int ksize, int stride) {
+  WgradParams p = {};
+  if (wgrad2d_geometry(p, N, H, W, Cin, Cout, ksize, stride)) return -1;
+  return p.splits > 1 ? (int64_t)p.splits * p.taps * Cout * Cin : 0;
+}
+
+extern "C" int sgc_conv2d_wgrad_bf16x3(const float *x, const float *dy, float *dw, int N, int H, int W, int Cin, int Cout, int ksize,
+                                       int stride, float *workspace_or_null, int64_t workspace_floats, sgc_stream_t stream) {
+  if (!x || !dy || !dw) return set_error(SGC_EINVAL, "sgc_conv2d_wgrad_bf16x3: null pointer");
+  if (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dw | (uintptr_t)workspace_or_null) & 15)
+    return set_error(SGC_EINVAL, "sgc_conv2d_wgrad_bf16x3: pointers must be 16-byte aligned");
+  WgradParams p = {};
+  const int rc = wgrad2d_geometry(p, N, H, W, Cin, Cout, ksize, stride);
   if (rc) return rc;
-  if (p.splits > 1) {
-    const int64_t n4 = n / 4;
-    const int g = (int)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096);
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(g), dim3(256), 0, st, reinterpret_cast<const float4 *>(workspace_or_null),
-                       reinterpret_cast<float4 *>(dw), n4, p.splits);
-    rc = check_launch("wgrad_reduce_kernel");
-  }
-  return rc;
+  return wgrad_tile_launch<true>(p, x, dy, dw, workspace_or_null, workspace_floats, stream);
 }

@@ -420,6 +420,92 @@ class ChannelsLastConv3dFunction(Function):
         return dx, dw, None, None, None
 
 
+class FrozenNormConv2dFunction(Function):
+    """``act(norm(nn.Conv2d(k, stride, padding=k//2, bias=False)(x)) [+ residual])`` with a FROZEN norm (eval statistics, no
+    gradient to its parameters: the ResNet backbone in every reference config) on channels-last rows, all three passes on the
+    MFMA kernels.  The norm is the folded per-channel ``scale`` / ``shift`` of the eval lowering, so the
+    forward is the eval forward: the same entry points and epilogues as ``Conv2dSpec.__call__``.
+
+    ``apply(x, weight, scale, shift, residual, nhw, stride, relu, relu_after_add)``: x [N*H*W, Cin] rows, weight
+    [Cout, Cin, k, k] (the module's parameter), scale / shift [Cout] | None, residual [N*OH*OW, Cout] | None, nhw = (N, H, W)
+    -> y [N*OH*OW, Cout], OH = ceil(H / stride).  Cin % 32 == 0, Cout % 32 == 0, k in {1, 3}, stride in {1, 2}.
+    ``relu``: ReLU behind the norm (no residual); ``relu_after_add``: ReLU behind the skip addition.  ``relu`` WITH a residual
+    (``relu(t) + residual``) is refused: its gate cannot be read off y.
+
+    * backward of the epilogue: ``sgc_frozen_norm_act_backward`` (gate y > 0, times scale; the gated dy is the residual's gradient);
+    * input gradient: stride 1 -- the forward entry on g with the taps mirrored and Cin / Cout swapped; 3x3 stride 2 -- the
+      transposed form of ``sgc_conv2d_nhwc_ex_bf16x3`` (sums by output parity, 2.25 taps per pixel), cropped to H x W when a
+      side is odd; 1x1 stride 2 -- the 1x1 GEMM on g, written to the even positions of a zeroed map;
+    * weight gradient: ``sgc_conv2d_wgrad_bf16x3``.
+    x, y and the weight are saved; a layer's y is the next layer's x, so nothing is kept twice."""
+
+    @staticmethod
+    def forward(ctx, x, weight, scale, shift, residual, nhw, stride, relu, relu_after_add):
+        _require_bf16_planes("FrozenNormConv2dFunction")
+        ops = ext.ops()
+        cout, cin, k = weight.shape[0], weight.shape[1], weight.shape[2]
+        N, H, W = nhw
+        if weight.dim() != 4 or weight.shape[3] != k or k not in (1, 3) or stride not in (1, 2) or cin % 32 or cout % 32:
+            raise RuntimeError("FrozenNormConv2dFunction: needs a [Cout, Cin, k, k] weight, k in {1, 3}, stride in {1, 2}, Cin % 32 == 0, Cout % 32 == 0")
+        if relu and residual is not None:
+            raise RuntimeError("FrozenNormConv2dFunction: relu(norm(conv)) + residual has no gate in its output; "
+                               "use relu_after_add (the ReLU behind the skip addition)")
+        if relu and relu_after_add:
+            raise RuntimeError("FrozenNormConv2dFunction: relu and relu_after_add exclude each other")
+        hi, lo = _TRAIN_PLANES.get(weight)                     # [k*k, Cout, Cin]
+        x = x.float().contiguous()
+        res = None if residual is None else residual.detach().float().contiguous()
+        scale = None if scale is None else scale.detach().float().contiguous()
+        shift = None if shift is None else shift.detach().float().contiguous()
+        if stride == 2 and (H % 2 or W % 2):
+            y = ops.conv2d_nhwc_strided_bf16x3(x, hi, lo, nhw, k, stride=2, scale=scale, shift=shift, residual=res, relu=relu,
+                                               relu_after_add=relu_after_add)
+        elif stride == 1 and not relu_after_add:
+            y = ops.conv2d_nhwc_bf16x3(x, hi, lo, nhw, k, scale=scale, shift=shift, residual=res, relu=1 if relu else 0)
+        else:
+            y = ops.conv2d_nhwc_ex_bf16x3(x, hi, lo, nhw, k, stride=stride, scale=scale, shift=shift, residual=res, relu=relu,
+                                          relu_after_add=relu_after_add)
+        ctx.save_for_backward(x, y, weight, scale)
+        ctx.geom = (tuple(nhw), k, stride, bool(relu or relu_after_add), residual is not None)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        ops = ext.ops()
+        x, y, weight, scale = ctx.saved_tensors
+        (N, H, W), k, stride, gated, has_res = ctx.geom
+        OH, OW = (H + stride - 1) // stride, (W + stride - 1) // stride
+        cin = weight.shape[1]
+        dy = dy.float().contiguous()
+        want_res = has_res and ctx.needs_input_grad[4]
+        if gated or scale is not None:
+            g, gres = ops.frozen_norm_act_backward(dy, y if gated else None, scale, relu=gated, want_gres=want_res and gated)
+            if want_res and not gated:
+                gres = dy
+        else:
+            g, gres = dy, (dy if want_res else None)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            if stride == 1:
+                hi, lo = _TRAIN_PLANES.get(weight, transpose=True, flip=True)        # [k*k, Cin, Cout], taps mirrored
+                dx = ops.conv2d_nhwc_bf16x3(g, hi, lo, (N, H, W), k)
+            elif k == 3:
+                hi, lo = _TRAIN_PLANES.get(weight, transpose=True)                   # the ConvTranspose2d reading of the parameter
+                up = ops.conv2d_nhwc_ex_bf16x3(g, hi, lo, (N, OH, OW), 3, stride=2, transposed=True)       # [N * 2 OH * 2 OW, Cin]
+                dx = up if (2 * OH, 2 * OW) == (H, W) else up.view(N, 2 * OH, 2 * OW, cin)[:, :H, :W].reshape(N * H * W, cin)
+            else:
+                hi, lo = _TRAIN_PLANES.get(weight, transpose=True)
+                t = ops.conv2d_nhwc_bf16x3(g, hi, lo, (N, OH, OW), 1)
+                dx = torch.zeros((N, H, W, cin), dtype=torch.float32, device=g.device)
+                dx[:, ::2, ::2] = t.view(N, OH, OW, cin)
+                dx = dx.view(N * H * W, cin)
+        if ctx.needs_input_grad[1]:
+            dwk = ops.conv2d_wgrad_bf16x3(x, g, (N, H, W), k, stride)               # [k*k, Cout, Cin]
+            dw = ops.unpack_conv_wgrad(dwk, weight.shape).to(weight.dtype)
+        return dx, dw, None, None, gres, None, None, None, None
+
+
 class ChannelsLastConvTranspose3dFunction(Function):
     """``nn.ConvTranspose3d(2, 2, bias=False)`` on channels-last rows (up_block_*, necks/imvoxelnet.py:56-58): forward on the
     parity form of the MFMA kernel, input gradient = the k2 s2 convolution of dy, weight gradient =

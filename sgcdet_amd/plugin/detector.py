@@ -91,12 +91,20 @@ class SGCDet(nn.Module):
         return self.simple_test(batch)
 
     def forward_train(self, batch):
-        """SGCDet.forward_train (SGCDet.py:98-114): the losses of a batch from images on (the backbone runs its torch
-        formulation under autograd)."""
+        """SGCDet.forward_train (SGCDet.py:98-114): the losses of a batch from images on.  The backbone trains on the HIP
+        kernels when its norms are frozen (plugin/resnet.py ``_forward_hip_train``), so the step's weight planes are repacked
+        here, before it runs."""
         self._need_backbone("forward_train")
-        x = self.extract_img_feat(batch["img"])
-        return self.forward_train_from_fpn(x, batch["img"], batch["img_metas"], batch["gt_bboxes_3d"], batch["gt_labels_3d"],
-                                           batch.get("depth_maps"))
+        if self.training and torch.is_grad_enabled():
+            from ..functions import train_weight_planes
+            train_weight_planes().begin_step()
+            self._step_begun = True                    # build_volume_from_features does not begin the step a second time
+        try:
+            x = self.extract_img_feat(batch["img"])
+            return self.forward_train_from_fpn(x, batch["img"], batch["img_metas"], batch["gt_bboxes_3d"], batch["gt_labels_3d"],
+                                               batch.get("depth_maps"))
+        finally:
+            self._step_begun = False
 
     def image_features(self, backbone_feats):
         """Backbone maps [[B*N, C_l, H_l, W_l], ...] -> [[B, N, C, H, W], ...] as SGCDet.py:67-69 with B = 1.  In eval mode on
@@ -143,7 +151,7 @@ class SGCDet(nn.Module):
         return volume, valid, dpt_dist, occ
 
     def build_volume_from_features(self, x, img_metas, dpt_dist):
-        if self.training and torch.is_grad_enabled():
+        if self.training and torch.is_grad_enabled() and not getattr(self, "_step_begun", False):
             # a training step begins: every weight plane the HIP training Functions have registered is repacked in ONE launch
             from ..functions import train_weight_planes
             train_weight_planes().begin_step()

@@ -15,9 +15,16 @@ channels-last rows: the stem on ``sgc_conv2d_stem7_bf16x3``, the pooling on ``sg
 convolutions on the image tile kernels with eval BatchNorm folded into the epilogues and the ReLUs / skip additions inside
 them; stride-2 layers over maps with an odd side (15 x 20 -> 8 x 10 at the reference geometry) on
 ``sgc_conv2d_nhwc_strided_bf16x3``.  The returned maps are logical NCHW and channels-last in memory: ``FPN._forward_hip``
-reads them in place.  Training, autograd and CPU tensors take the torch formulation; ``SGC_BACKBONE_HIP=0`` restores it for the
-eval forward too (A/B runs).  An image with an odd side, ``in_channels != 3``, ``base_channels != 64`` or a non-fp32 input
-runs the torch formulation as well.
+reads them in place.  ``SGC_BACKBONE_HIP=0`` restores the torch formulation for the eval forward (A/B runs).  An image with an
+odd side, ``in_channels != 3``, ``base_channels != 64`` or a non-fp32 input runs the torch formulation as well.
+
+Training under autograd with every norm frozen -- the reference configuration: ``frozen_stages=1``, ``norm_eval=True``,
+``norm_cfg.requires_grad=False`` -- runs on the kernels too (``_forward_hip_train``): the frozen prefix (stem,
+pooling, leading blocks without a trainable parameter) is the eval lowering under ``no_grad``; from the first trainable block
+on every layer is a ``functions.FrozenNormConv2dFunction`` -- the eval forward with its folded scale / shift and fused
+ReLU / skip epilogues, the input gradient on the forward kernels and the weight gradient on ``sgc_conv2d_wgrad_bf16x3``.
+``SGC_BACKBONE_TRAIN_HIP=0`` keeps the torch formulation; a norm in training mode or with trainable parameters, a trainable
+stem, CPU tensors and the fp16 arithmetic mode take it as well.
 """
 import os
 
@@ -31,6 +38,7 @@ from . import conv_plan
 from .conv_plan import Conv2dSpec, cached_plan
 
 HIP_DEFAULT = "1"      # SGC_BACKBONE_HIP when the environment does not set it (DESIGN.md 4.11 says how it was chosen)
+TRAIN_HIP_DEFAULT = "1"      # SGC_BACKBONE_TRAIN_HIP when the environment does not set it (DESIGN.md 4.12 says how it was chosen)
 
 
 def _norm(channels, norm_cfg):
@@ -124,6 +132,38 @@ def run_block(B, x, nhw):
     identity = B["down"](x, nhw, relu=False)[0] if "down" in B else x
     last = B["conv3"] if "conv3" in B else B["conv2"]
     return last(y, n1, residual=identity, relu=False, relu_after_add=True)[0], n1  # relu(bn(conv) + identity)
+
+
+def _train_layers(b):
+    """The convolutions of a block with the norms behind them, in the order ``run_block_train`` applies them."""
+    d = dict(conv1=(b.conv1, b.bn1), conv2=(b.conv2, b.bn2))
+    if isinstance(b, Bottleneck):
+        d["conv3"] = (b.conv3, b.bn3)
+    if b.downsample is not None:
+        d["down"] = (b.downsample[0], b.downsample[1])
+    return d
+
+
+def run_block_train(b, T, x, nhw, keep=None):
+    """Block ``b`` on rows ``x`` under autograd: the layer order and epilogues of ``run_block``, every layer a
+    ``FrozenNormConv2dFunction`` on the module's own weight.  ``T``: layer name -> (scale, shift), the folded frozen norm.
+    ``keep``: a list that receives every layer's output rows in the order they are computed."""
+    from ..functions import FrozenNormConv2dFunction
+    L = _train_layers(b)
+
+    def layer(name, inp, inhw, residual=None, relu=True, relu_after_add=False):
+        conv = L[name][0]
+        s = conv.stride[0]
+        y = FrozenNormConv2dFunction.apply(inp, conv.weight, T[name][0], T[name][1], residual, inhw, s, relu, relu_after_add)
+        if keep is not None:
+            keep.append(y)
+        return y, (inhw[0], (inhw[1] + s - 1) // s, (inhw[2] + s - 1) // s)
+
+    y, n1 = layer("conv1", x, nhw)
+    if "conv3" in L:
+        y, n1 = layer("conv2", y, n1)
+    identity = layer("down", x, nhw, relu=False)[0] if "down" in L else x
+    return layer("conv3" if "conv3" in L else "conv2", y, n1, residual=identity, relu=False, relu_after_add=True)[0], n1
 
 
 @BACKBONES.register_module()
@@ -246,9 +286,80 @@ class ResNet(BaseModule):
                 outs.append(x.view(nhw[0], nhw[1], nhw[2], x.shape[1]).permute(0, 3, 1, 2))   # logical NCHW, channels-last memory
         return tuple(outs)
 
+    # ---- training with frozen norms: the eval lowering under autograd ---------------------------------------
+    def blocks(self):
+        """The residual blocks in forward order."""
+        return [b for name in self.res_layers for b in getattr(self, name)]
+
+    def frozen_prefix(self):
+        """How many leading blocks have no parameter that requires a gradient (they run the eval lowering in training)."""
+        n = 0
+        for b in self.blocks():
+            if any(p.requires_grad for p in b.parameters()):
+                break
+            n += 1
+        return n
+
+    def _train_hip_config_ok(self):
+        """The tensor-independent part of the training-path predicate: training mode, every norm frozen (eval statistics, no
+        trainable parameter), a frozen stem, the bf16 weight planes' arithmetic modes and the environment switch."""
+        norms = [m for m in self.modules() if isinstance(m, nn.modules.batchnorm._BatchNorm)]
+        return (self.training and self.frozen_stages >= 0 and not any(p.requires_grad for p in self.conv1.parameters())
+                and not any(m.training for m in norms) and not any(p.requires_grad for m in norms for p in m.parameters())
+                and conv_plan.CONV_MODE == "bf16x3" and conv_plan.train_products_ok()
+                and os.environ.get("SGC_BACKBONE_TRAIN_HIP", TRAIN_HIP_DEFAULT) != "0")
+
+    def _train_plan(self):
+        """The frozen prefix as eval plan entries and the folded (scale, shift) of every trainable layer.  Rebuilt when a
+        tensor of the prefix or of a norm changes -- not when a trainable weight does: those are read through
+        ``train_weight_planes()`` every step."""
+        blocks = self.blocks()
+        nf = self.frozen_prefix()
+        norms = [m for m in self.modules() if isinstance(m, nn.modules.batchnorm._BatchNorm)]
+        watched = ([self.conv1.weight] + [t for b in blocks[:nf] for t in b.parameters()]
+                   + [t for m in norms for t in list(m.parameters()) + list(m.buffers())])
+        fp = (conv_plan.CONV_PRODUCTS, nf) + tuple((t.data_ptr(), t._version) for t in watched)
+
+        def build():
+            stem = Conv2dSpec(self.conv1, self.bn1, pad_in=False)
+            stem.set_weight(F.pad(stem.w.permute(1, 2, 0).reshape(64, 147), (0, 13)).contiguous())
+            train = [{name: tuple(t.contiguous() for t in conv_plan.fold_norm(conv.out_channels, bn, conv.bias, conv.weight.device))
+                      for name, (conv, bn) in _train_layers(b).items()} for b in blocks[nf:]]
+            return dict(stem=stem, frozen=[_block_specs(b) for b in blocks[:nf]], train=train)
+        return cached_plan(self, build, attr="_hip_train_plan", fingerprint=fp)
+
+    def _forward_hip_train(self, img, keep=None):
+        """The training forward on the kernels (see the module docstring).  ``keep``: a list that receives the output rows of
+        every trainable layer in layer order (their signs are the ReLU gates of the backward)."""
+        ops = ext.ops()
+        P = self._train_plan()
+        blocks = self.blocks()
+        nf = len(P["frozen"])
+        N, _, Hi, Wi = img.shape
+        with torch.no_grad():
+            st = P["stem"]
+            x = ops.conv2d_stem7_bf16x3(img.contiguous(), st.w_hi, st.w_lo, scale=st.scale, shift=st.shift, relu=True)
+            x, nhw = ops.maxpool2d_nhwc(x, (N, Hi // 2, Wi // 2))
+        outs, i = [], 0
+        for s, name in enumerate(self.res_layers):
+            for _ in getattr(self, name):
+                if i < nf:
+                    with torch.no_grad():
+                        x, nhw = run_block(P["frozen"][i], x, nhw)
+                else:
+                    x, nhw = run_block_train(blocks[i], P["train"][i - nf], x, nhw, keep)
+                i += 1
+            if s in self.out_indices:
+                outs.append(x.view(nhw[0], nhw[1], nhw[2], x.shape[1]).permute(0, 3, 1, 2))   # logical NCHW, channels-last memory
+        return tuple(outs)
+
     def forward(self, x):
         """img [B*N, 3, H, W] -> the ``out_indices`` maps [B*N, C_l, H_l, W_l].  Eval mode on the GPU without autograd:
-        ``_forward_hip`` (the maps are channels-last in memory); otherwise the torch formulation."""
+        ``_forward_hip``; training under autograd with frozen norms: ``_forward_hip_train`` (both return maps that are
+        channels-last in memory); otherwise the torch formulation."""
+        if (self.training and torch.is_grad_enabled() and x.is_cuda and not x.requires_grad and self._train_hip_config_ok()
+                and self._hip_ok(x)):
+            return self._forward_hip_train(x)
         if (not self.training and not torch.is_grad_enabled() and x.is_cuda
                 and os.environ.get("SGC_BACKBONE_HIP", HIP_DEFAULT) != "0" and self._hip_ok(x)):
             return self._forward_hip(x)

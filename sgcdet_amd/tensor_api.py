@@ -1151,6 +1151,45 @@ class TensorOps:
                    _meta=dict(V=OV, Cin=Cin, Cout=Cout, taps=ksize ** 3, OV=OV))
         return dw
 
+    def conv2d_wgrad_workspace_floats(self, nhw, Cin, Cout, ksize, stride=1):
+        """Floats of the workspace ``conv2d_wgrad_bf16x3`` sums its split reduction through; 0: the shape is not split."""
+        N, H, W = nhw
+        n = int(self.lib._dll.sgc_conv2d_wgrad_workspace_floats(N, H, W, Cin, Cout, ksize, stride))
+        if n < 0:
+            raise RuntimeError("conv2d_wgrad_bf16x3: " + self.lib.last_error())
+        return n
+
+    def conv2d_wgrad_bf16x3(self, x, dy, nhw, ksize, stride=1, workspace=True):
+        """dW [ksize^2, Cout, Cin] of ``nn.Conv2d(k, stride, padding=k//2)`` over channels-last rows: x [N*H*W, Cin], dy
+        [N*ceil(H/s)*ceil(W/s), Cout] (``sgc_conv2d_wgrad_bf16x3``, include/sgcdet_amd_train.h).  ``workspace=False``: no
+        workspace is passed, one workgroup per tile walks the whole reduction."""
+        self._check(x=x, dy=dy)
+        self._f32(x=x, dy=dy)
+        N, H, W = nhw
+        OH, OW = (H + stride - 1) // stride, (W + stride - 1) // stride
+        if x.dim() != 2 or dy.dim() != 2 or x.shape[0] != N * H * W or dy.shape[0] != N * OH * OW:
+            raise RuntimeError("conv2d_wgrad_bf16x3: inconsistent shapes")
+        Cin, Cout = x.shape[1], dy.shape[1]
+        n = self.conv2d_wgrad_workspace_floats(nhw, Cin, Cout, ksize, stride) if workspace else 0
+        ws = torch.empty(n, dtype=torch.float32, device=x.device) if n > 0 else None
+        dw = torch.empty((ksize * ksize, Cout, Cin), dtype=torch.float32, device=x.device)
+        self._call("sgc_conv2d_wgrad_bf16x3", x, dy, dw, N, H, W, Cin, Cout, ksize, stride, ws, n,
+                   _meta=dict(V=dy.shape[0], Cin=Cin, Cout=Cout, taps=ksize * ksize, OV=dy.shape[0]))
+        return dw
+
+    def frozen_norm_act_backward(self, dy, y=None, scale=None, relu=False, want_gres=False):
+        """Backward of a frozen-norm epilogue (``sgc_frozen_norm_act_backward``): dy, y [rows, C] -> (g, gres | None) with
+        g = gate * dy * scale, gres = gate * dy, gate = (y > 0) with ``relu`` else 1."""
+        self._check(dy=dy, y=y, scale=scale)
+        self._f32(dy=dy, y=y, scale=scale)
+        if dy.dim() != 2 or (relu and (y is None or y.shape != dy.shape)) or (scale is not None and scale.numel() != dy.shape[1]):
+            raise RuntimeError("frozen_norm_act_backward: inconsistent shapes")
+        g = torch.empty_like(dy)
+        gres = torch.empty_like(dy) if want_gres else None
+        if dy.numel():
+            self._call("sgc_frozen_norm_act_backward", dy, y if relu else None, scale, g, gres, dy.shape[0], dy.shape[1], int(bool(relu)))
+        return g, gres
+
     def _conv_workspace(self, device, ix, iy, iz, Cin, Cout, ksize, stride, transposed, bf16x3):
         """Split-K layers get a workspace so that their partial sums are added in a fixed order (bit-identical
         results from run to run); (None, 0) for layers that are not split."""
