@@ -424,7 +424,8 @@ class FrozenNormConv2dFunction(Function):
     """``act(norm(nn.Conv2d(k, stride, padding=k//2, bias=False)(x)) [+ residual])`` with a FROZEN norm (eval statistics, no
     gradient to its parameters: the ResNet backbone in every reference config) on channels-last rows, all three passes on the
     MFMA kernels.  The norm is the folded per-channel ``scale`` / ``shift`` of the eval lowering, so the
-    forward is the eval forward: the same entry points and epilogues as ``Conv2dSpec.__call__``.
+    forward is the eval forward: both reach the entry points through ``conv_plan.conv2d_rows``, the one dispatch rule, and so
+    do the input gradients below.  ``conv_plan.FrozenConv2d`` wraps this Function in ``Conv2dSpec``'s call signature.
 
     ``apply(x, weight, scale, shift, residual, nhw, stride, relu, relu_after_add)``: x [N*H*W, Cin] rows, weight
     [Cout, Cin, k, k] (the module's parameter), scale / shift [Cout] | None, residual [N*OH*OW, Cout] | None, nhw = (N, H, W)
@@ -441,10 +442,9 @@ class FrozenNormConv2dFunction(Function):
 
     @staticmethod
     def forward(ctx, x, weight, scale, shift, residual, nhw, stride, relu, relu_after_add):
+        from .plugin.conv_plan import conv2d_rows
         _require_bf16_planes("FrozenNormConv2dFunction")
-        ops = ext.ops()
         cout, cin, k = weight.shape[0], weight.shape[1], weight.shape[2]
-        N, H, W = nhw
         if weight.dim() != 4 or weight.shape[3] != k or k not in (1, 3) or stride not in (1, 2) or cin % 32 or cout % 32:
             raise RuntimeError("FrozenNormConv2dFunction: needs a [Cout, Cin, k, k] weight, k in {1, 3}, stride in {1, 2}, Cin % 32 == 0, Cout % 32 == 0")
         if relu and residual is not None:
@@ -457,14 +457,7 @@ class FrozenNormConv2dFunction(Function):
         res = None if residual is None else residual.detach().float().contiguous()
         scale = None if scale is None else scale.detach().float().contiguous()
         shift = None if shift is None else shift.detach().float().contiguous()
-        if stride == 2 and (H % 2 or W % 2):
-            y = ops.conv2d_nhwc_strided_bf16x3(x, hi, lo, nhw, k, stride=2, scale=scale, shift=shift, residual=res, relu=relu,
-                                               relu_after_add=relu_after_add)
-        elif stride == 1 and not relu_after_add:
-            y = ops.conv2d_nhwc_bf16x3(x, hi, lo, nhw, k, scale=scale, shift=shift, residual=res, relu=1 if relu else 0)
-        else:
-            y = ops.conv2d_nhwc_ex_bf16x3(x, hi, lo, nhw, k, stride=stride, scale=scale, shift=shift, residual=res, relu=relu,
-                                          relu_after_add=relu_after_add)
+        y = conv2d_rows(x, hi, lo, nhw, k, stride, scale=scale, shift=shift, residual=res, relu=relu, relu_after_add=relu_after_add)
         ctx.save_for_backward(x, y, weight, scale)
         ctx.geom = (tuple(nhw), k, stride, bool(relu or relu_after_add), residual is not None)
         return y
@@ -487,16 +480,17 @@ class FrozenNormConv2dFunction(Function):
             g, gres = dy, (dy if want_res else None)
         dx = dw = None
         if ctx.needs_input_grad[0]:
+            from .plugin.conv_plan import conv2d_rows
             if stride == 1:
                 hi, lo = _TRAIN_PLANES.get(weight, transpose=True, flip=True)        # [k*k, Cin, Cout], taps mirrored
-                dx = ops.conv2d_nhwc_bf16x3(g, hi, lo, (N, H, W), k)
+                dx = conv2d_rows(g, hi, lo, (N, H, W), k, relu=False)
             elif k == 3:
                 hi, lo = _TRAIN_PLANES.get(weight, transpose=True)                   # the ConvTranspose2d reading of the parameter
-                up = ops.conv2d_nhwc_ex_bf16x3(g, hi, lo, (N, OH, OW), 3, stride=2, transposed=True)       # [N * 2 OH * 2 OW, Cin]
+                up = conv2d_rows(g, hi, lo, (N, OH, OW), 3, stride=2, transposed=True, relu=False)       # [N * 2 OH * 2 OW, Cin]
                 dx = up if (2 * OH, 2 * OW) == (H, W) else up.view(N, 2 * OH, 2 * OW, cin)[:, :H, :W].reshape(N * H * W, cin)
             else:
                 hi, lo = _TRAIN_PLANES.get(weight, transpose=True)
-                t = ops.conv2d_nhwc_bf16x3(g, hi, lo, (N, OH, OW), 1)
+                t = conv2d_rows(g, hi, lo, (N, OH, OW), 1, relu=False)
                 dx = torch.zeros((N, H, W, cin), dtype=torch.float32, device=g.device)
                 dx[:, ::2, ::2] = t.view(N, OH, OW, cin)
                 dx = dx.view(N * H * W, cin)

@@ -1,8 +1,10 @@
 """What the eval-mode lowerings of the plugin modules share: a module's layers prepared once for the library's kernels.
 
-``ConvSpec`` (3-D: neck and head, ``sgc_conv3d_cl_*`` / Winograd-z), ``Conv2dSpec`` (2-D: backbone, FPN and depth net,
-``sgc_conv2d_nhwc_bf16x3`` / ``sgc_conv2d_nhwc_ex_bf16x3`` / ``sgc_conv2d_nhwc_strided_bf16x3``), ``LinearSpec`` and ``BlockDiagSpec`` (the row GEMMs of the
-transformer) each hold one layer as the kernels take it and dispatch it in ``__call__``.  Eval BatchNorm (running statistics)
+``ConvSpec`` (3-D: neck and head, ``sgc_conv3d_cl_*`` / Winograd-z), ``Conv2dSpec`` (2-D: backbone, FPN and depth net),
+``LinearSpec`` and ``BlockDiagSpec`` (the row GEMMs of the transformer) each hold one layer as the kernels take it and dispatch
+it in ``__call__``.  ``conv2d_rows`` is the one rule that sends a 2-D layer to ``sgc_conv2d_nhwc_bf16x3`` /
+``sgc_conv2d_nhwc_ex_bf16x3`` / ``sgc_conv2d_nhwc_strided_bf16x3``: ``Conv2dSpec`` and its training twin ``FrozenConv2d`` (frozen
+norm, autograd) both reach the entries through it, so the training forward is the eval forward.  Eval BatchNorm (running statistics)
 and the bias are folded into a per-channel scale / shift for the kernel's epilogue (``fold_norm``, the only copy), weights are
 permuted once to ``[tap][Cout][Cin]``, and channel counts are zero-padded to multiples of 32 (the K tile; ``_pad_to``) with zero
 weight rows, scale 1 and shift 0, so padded output columns are exactly 0.  ``cached_plan`` keeps a module's plan and rebuilds it
@@ -172,28 +174,57 @@ class Conv2dSpec:
         self.w_hi, self.w_lo = ext.ops().split_operand(w) if w.is_cuda else (None, None)
 
     def __call__(self, x, nhw, residual=None, relu=True, relu_after_add=False, out=None, col0=0, softmax_cols=0):
-        """The layer on rows ``x``; returns (rows, (N, OH, OW)).  Plain stride-1 layers go to the halo form of
-        ``sgc_conv2d_nhwc_bf16x3`` (its `relu = 2`: ReLU, then the skip), everything else to ``sgc_conv2d_nhwc_ex_bf16x3``; a
-        stride-2 layer over a map with an odd side to ``sgc_conv2d_nhwc_strided_bf16x3`` (output ceil(H / 2) x ceil(W / 2), the
-        ResNet stages: DESIGN.md 4.11)."""
-        ops = ext.ops()
+        """The layer on rows ``x`` through ``conv2d_rows``; returns (rows, (N, OH, OW))."""
         N, H, W = nhw
         s = self.stride
         onhw = (N, 2 * H, 2 * W) if self.transposed else (N, (H + s - 1) // s, (W + s - 1) // s)
-        if s == 2 and not self.transposed and (H % 2 or W % 2):
-            y = ops.conv2d_nhwc_strided_bf16x3(x, self.w_hi, self.w_lo, nhw, self.k, stride=s, scale=self.scale, shift=self.shift,
-                                               residual=residual, relu=relu, relu_after_add=relu_after_add, out=out, col0=col0,
-                                               softmax_cols=softmax_cols)
-            return y, onhw
-        if (self.stride == 1 and not self.transposed and out is None and not relu_after_add and softmax_cols == 0
-                and (residual is None or residual.shape[1] == self.w_hi.shape[1])):
-            mode = (2 if residual is not None else 1) if relu else 0
-            return ops.conv2d_nhwc_bf16x3(x, self.w_hi, self.w_lo, nhw, self.k, scale=self.scale, shift=self.shift,
-                                          residual=residual, relu=mode), onhw
-        y = ops.conv2d_nhwc_ex_bf16x3(x, self.w_hi, self.w_lo, nhw, self.k, stride=self.stride, transposed=self.transposed,
-                                      scale=self.scale, shift=self.shift, residual=residual, relu=relu,
-                                      relu_after_add=relu_after_add, out=out, col0=col0, softmax_cols=softmax_cols)
-        return y, onhw
+        return conv2d_rows(x, self.w_hi, self.w_lo, nhw, self.k, s, self.transposed, self.scale, self.shift, residual, relu,
+                           relu_after_add, out, col0, softmax_cols), onhw
+
+
+def conv2d_rows(x, w_hi, w_lo, nhw, k, stride=1, transposed=False, scale=None, shift=None, residual=None, relu=True,
+                relu_after_add=False, out=None, col0=0, softmax_cols=0):
+    """THE dispatch of a 2-D layer on rows ``x`` [N*H*W, Cin] with planes [k*k, Cout, Cin] to its forward entry; returns the
+    output rows.  ``Conv2dSpec`` (eval) and ``FrozenNormConv2dFunction`` (training: its forward and its input gradients) both
+    come through here, so one layer takes one entry in both.  In this order: a stride-2 layer over a map with an odd side ->
+    ``sgc_conv2d_nhwc_strided_bf16x3`` (output ceil(H / 2) x ceil(W / 2), the ResNet stages: DESIGN.md 4.11); a plain stride-1
+    layer -> ``sgc_conv2d_nhwc_bf16x3`` (`relu` = 0: no ReLU; 1: ReLU; 2: ReLU, then the skip); everything else -- transposed,
+    ReLU behind the skip, an ``out`` buffer, a wider residual, a softmax -> ``sgc_conv2d_nhwc_ex_bf16x3``."""
+    ops = ext.ops()
+    if stride == 2 and not transposed and (nhw[1] % 2 or nhw[2] % 2):
+        return ops.conv2d_nhwc_strided_bf16x3(x, w_hi, w_lo, nhw, k, stride=stride, scale=scale, shift=shift, residual=residual,
+                                              relu=relu, relu_after_add=relu_after_add, out=out, col0=col0, softmax_cols=softmax_cols)
+    if (stride == 1 and not transposed and out is None and not relu_after_add and softmax_cols == 0
+            and (residual is None or residual.shape[1] == w_hi.shape[1])):
+        mode = (2 if residual is not None else 1) if relu else 0
+        return ops.conv2d_nhwc_bf16x3(x, w_hi, w_lo, nhw, k, scale=scale, shift=shift, residual=residual, relu=mode)
+    return ops.conv2d_nhwc_ex_bf16x3(x, w_hi, w_lo, nhw, k, stride=stride, transposed=transposed, scale=scale, shift=shift,
+                                     residual=residual, relu=relu, relu_after_add=relu_after_add, out=out, col0=col0,
+                                     softmax_cols=softmax_cols)
+
+
+def stem7_spec(conv, bn):
+    """The 7x7 stride-2 stem as ``sgc_conv2d_stem7_bf16x3`` reads it: [49, 64, 3] -> the [64, 160] matrix, column
+    (ci * 7 + kh) * 7 + kw, 147..159 zero."""
+    stem = Conv2dSpec(conv, bn, pad_in=False)
+    stem.set_weight(torch.nn.functional.pad(stem.w.permute(1, 2, 0).reshape(64, 147), (0, 13)).contiguous())
+    return stem
+
+
+class FrozenConv2d:
+    """To training what ``Conv2dSpec`` is to eval, with its call signature: an ``nn.Conv2d`` with a FROZEN norm behind it,
+    under autograd (``functions.FrozenNormConv2dFunction``).  Holds the module -- its weight is read live through
+    ``train_weight_planes()`` at every call -- and the folded (scale, shift)."""
+
+    def __init__(self, conv, bn):
+        self.conv = conv
+        self.scale, self.shift = (t.contiguous() for t in fold_norm(conv.out_channels, bn, conv.bias, conv.weight.device))
+
+    def __call__(self, x, nhw, residual=None, relu=True, relu_after_add=False):
+        from ..functions import FrozenNormConv2dFunction
+        s = self.conv.stride[0]
+        y = FrozenNormConv2dFunction.apply(x, self.conv.weight, self.scale, self.shift, residual, nhw, s, relu, relu_after_add)
+        return y, (nhw[0], (nhw[1] + s - 1) // s, (nhw[2] + s - 1) // s)
 
 
 # training / autograd path of the neck and head convolutions: "hip" = forward, input and weight gradients on the MFMA

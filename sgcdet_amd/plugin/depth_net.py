@@ -34,7 +34,7 @@ import torch.nn.functional as F
 
 from .. import ext
 from ..mmcv_lite import HEADS
-from .conv_plan import Conv2dSpec, cached_plan, image_rows
+from .conv_plan import Conv2dSpec, cached_plan, image_rows, stem7_spec
 from .plane_sweep import closest_frame_ids, plane_sweep_correlation
 
 
@@ -203,10 +203,7 @@ def depth_net_plan(net):
     ``fusion_regulation.conv11`` (whose skip is that buffer) are permuted to that order here.  ``cat_perm[new] = module index``."""
     D, f = net.depth_channels, net.fnet_mvs
     cat_perm = torch.cat([torch.arange(D, D + 128), torch.arange(D)]).to(net.depth_reg.weight.device)
-    stem = Conv2dSpec(f.conv1, f.bn1, pad_in=False)
-    # [49, 64, 3] -> [64, 160]: column (ci * 7 + kh) * 7 + kw, 147..159 zero
-    stem.set_weight(F.pad(stem.w.permute(1, 2, 0).reshape(64, 147), (0, 13)).contiguous())
-    return dict(stem=stem, blocks=[_block_layers(b) for b in list(f.layer1) + list(f.layer2)], final=Conv2dSpec(f.final_conv_3ddet),
+    return dict(stem=stem7_spec(f.conv1, f.bn1), blocks=[_block_layers(b) for b in list(f.layer1) + list(f.layer2)], final=Conv2dSpec(f.final_conv_3ddet),
                 corr=_unet_layers(net.correlation_regulation), fnet_mono=Conv2dSpec(net.fnet_mono.conv, net.fnet_mono.bn),
                 mono=_unet_layers(net.mono_regulation), fusion=_unet_layers(net.fusion_regulation, in_perm=cat_perm, out_perm=cat_perm),
                 depth_reg=Conv2dSpec(net.depth_reg, in_perm=cat_perm, pad_out=False), cat_perm=cat_perm)

@@ -19,10 +19,12 @@ reads them in place.  ``SGC_BACKBONE_HIP=0`` restores the torch formulation for 
 odd side, ``in_channels != 3``, ``base_channels != 64`` or a non-fp32 input runs the torch formulation as well.
 
 Training under autograd with every norm frozen -- the reference configuration: ``frozen_stages=1``, ``norm_eval=True``,
-``norm_cfg.requires_grad=False`` -- runs on the kernels too (``_forward_hip_train``): the frozen prefix (stem,
-pooling, leading blocks without a trainable parameter) is the eval lowering under ``no_grad``; from the first trainable block
-on every layer is a ``functions.FrozenNormConv2dFunction`` -- the eval forward with its folded scale / shift and fused
-ReLU / skip epilogues, the input gradient on the forward kernels and the weight gradient on ``sgc_conv2d_wgrad_bf16x3``.
+``norm_cfg.requires_grad=False`` -- runs on the kernels too (``_forward_hip_train``), and it IS the eval
+forward: one plan builder (``resnet_plan``), one block walker (``run_block``) and one forward (``_run_hip``) serve both, and
+every layer reaches its entry point through ``conv_plan.conv2d_rows``.  The frozen prefix (stem, pooling, leading blocks
+without a trainable parameter) is ``Conv2dSpec``s under ``no_grad``; from the first trainable block on every layer is a
+``conv_plan.FrozenConv2d`` (``functions.FrozenNormConv2dFunction``) -- the same folded scale / shift and fused ReLU / skip
+epilogues, the input gradient on the forward kernels and the weight gradient on ``sgc_conv2d_wgrad_bf16x3``.
 ``SGC_BACKBONE_TRAIN_HIP=0`` keeps the torch formulation; a norm in training mode or with trainable parameters, a trainable
 stem, CPU tensors and the fp16 arithmetic mode take it as well.
 """
@@ -30,12 +32,11 @@ import os
 
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
 from .. import ext
 from ..mmcv_lite import BACKBONES, BaseModule
 from . import conv_plan
-from .conv_plan import Conv2dSpec, cached_plan
+from .conv_plan import Conv2dSpec, FrozenConv2d, cached_plan, stem7_spec
 
 HIP_DEFAULT = "1"      # SGC_BACKBONE_HIP when the environment does not set it (DESIGN.md 4.11 says how it was chosen)
 TRAIN_HIP_DEFAULT = "1"      # SGC_BACKBONE_TRAIN_HIP when the environment does not set it (DESIGN.md 4.12 says how it was chosen)
@@ -103,67 +104,47 @@ class Bottleneck(nn.Module):
         return self.relu(out + identity)
 
 
-def _block_specs(b):
-    """One residual block as ``Conv2dSpec``s, eval BatchNorm folded (``conv3`` only in a Bottleneck, ``down`` only with a
-    projection shortcut)."""
-    d = dict(conv1=Conv2dSpec(b.conv1, b.bn1), conv2=Conv2dSpec(b.conv2, b.bn2))
+def _block_layers(b, make):
+    """One residual block as ``make(conv, norm)`` layers -- ``Conv2dSpec`` (eval BatchNorm folded, weight prepared) or
+    ``FrozenConv2d`` (the same fold, the live weight under autograd): ``conv3`` only in a Bottleneck, ``down`` only with a
+    projection shortcut."""
+    d = dict(conv1=make(b.conv1, b.bn1), conv2=make(b.conv2, b.bn2))
     if isinstance(b, Bottleneck):
-        d["conv3"] = Conv2dSpec(b.conv3, b.bn3)
+        d["conv3"] = make(b.conv3, b.bn3)
     if b.downsample is not None:
-        d["down"] = Conv2dSpec(b.downsample[0], b.downsample[1])
+        d["down"] = make(b.downsample[0], b.downsample[1])
     return d
 
 
-def resnet_plan(net):
-    """Every convolution of ``net`` (a ``ResNet`` in eval mode) as the kernels take it: the stem's [64, 160] matrix (column
-    (ci * 7 + kh) * 7 + kw, 147..159 zero) and, per stage, the blocks' layers."""
-    stem = Conv2dSpec(net.conv1, net.bn1, pad_in=False)
-    stem.set_weight(F.pad(stem.w.permute(1, 2, 0).reshape(64, 147), (0, 13)).contiguous())
-    return dict(stem=stem, stages=[[_block_specs(b) for b in getattr(net, name)] for name in net.res_layers])
+def resnet_plan(net, n_frozen=None):
+    """Every convolution of ``net`` as the kernels take it: the stem (``stem7_spec``) and, per stage, the blocks' layers.  The
+    first ``n_frozen`` blocks are ``Conv2dSpec``s, the rest ``FrozenConv2d``s; None: all prepared (the eval plan)."""
+    stages, i = [], 0
+    for name in net.res_layers:
+        stages.append([_block_layers(b, Conv2dSpec if n_frozen is None or i + j < n_frozen else FrozenConv2d)
+                       for j, b in enumerate(getattr(net, name))])
+        i += len(stages[-1])
+    return dict(stem=stem7_spec(net.conv1, net.bn1), stages=stages)
 
 
-def run_block(B, x, nhw):
-    """A planned block on rows ``x`` [N*H*W, C]: returns (rows, (N, OH, OW)).  The layer order and epilogues of the HIP path
-    (tests/test_resnet_cpu.py replays them with torch convolutions): the last convolution carries the skip addition and the
-    ReLU behind it; a projection shortcut is a convolution of its own without a ReLU."""
-    y, n1 = B["conv1"](x, nhw)                                                     # relu(bn1(conv1))
-    if "conv3" in B:
-        y, n1 = B["conv2"](y, n1)                                                  # relu(bn2(conv2)): the stride sits here
-    identity = B["down"](x, nhw, relu=False)[0] if "down" in B else x
-    last = B["conv3"] if "conv3" in B else B["conv2"]
-    return last(y, n1, residual=identity, relu=False, relu_after_add=True)[0], n1  # relu(bn(conv) + identity)
-
-
-def _train_layers(b):
-    """The convolutions of a block with the norms behind them, in the order ``run_block_train`` applies them."""
-    d = dict(conv1=(b.conv1, b.bn1), conv2=(b.conv2, b.bn2))
-    if isinstance(b, Bottleneck):
-        d["conv3"] = (b.conv3, b.bn3)
-    if b.downsample is not None:
-        d["down"] = (b.downsample[0], b.downsample[1])
-    return d
-
-
-def run_block_train(b, T, x, nhw, keep=None):
-    """Block ``b`` on rows ``x`` under autograd: the layer order and epilogues of ``run_block``, every layer a
-    ``FrozenNormConv2dFunction`` on the module's own weight.  ``T``: layer name -> (scale, shift), the folded frozen norm.
-    ``keep``: a list that receives every layer's output rows in the order they are computed."""
-    from ..functions import FrozenNormConv2dFunction
-    L = _train_layers(b)
-
-    def layer(name, inp, inhw, residual=None, relu=True, relu_after_add=False):
-        conv = L[name][0]
-        s = conv.stride[0]
-        y = FrozenNormConv2dFunction.apply(inp, conv.weight, T[name][0], T[name][1], residual, inhw, s, relu, relu_after_add)
+def run_block(B, x, nhw, keep=None):
+    """A planned block on rows ``x`` [N*H*W, C]: returns (rows, (N, OH, OW)).  THE layer order and epilogues of the HIP path, in
+    eval and in training alike (the layers of ``B`` are ``Conv2dSpec``s or ``FrozenConv2d``s; tests/test_resnet_cpu.py replays
+    them with torch convolutions): the last convolution carries the skip addition and the ReLU behind it; a projection shortcut
+    is a convolution of its own without a ReLU.  ``keep``: a list that receives every layer's output rows in the order they are
+    computed (conv1, [conv2,] down, last)."""
+    def layer(name, *args, **kw):
+        y, n = B[name](*args, **kw)
         if keep is not None:
             keep.append(y)
-        return y, (inhw[0], (inhw[1] + s - 1) // s, (inhw[2] + s - 1) // s)
+        return y, n
 
-    y, n1 = layer("conv1", x, nhw)
-    if "conv3" in L:
-        y, n1 = layer("conv2", y, n1)
-    identity = layer("down", x, nhw, relu=False)[0] if "down" in L else x
-    return layer("conv3" if "conv3" in L else "conv2", y, n1, residual=identity, relu=False, relu_after_add=True)[0], n1
+    y, n1 = layer("conv1", x, nhw)                                                 # relu(bn1(conv1))
+    if "conv3" in B:
+        y, n1 = layer("conv2", y, n1)                                              # relu(bn2(conv2)): the stride sits here
+    identity = layer("down", x, nhw, relu=False)[0] if "down" in B else x
+    last = "conv3" if "conv3" in B else "conv2"
+    return layer(last, y, n1, residual=identity, relu=False, relu_after_add=True)[0], n1       # relu(bn(conv) + identity)
 
 
 @BACKBONES.register_module()
@@ -271,20 +252,30 @@ class ResNet(BaseModule):
                 and self.base_channels == 64 and self.stem_channels == 64 and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0
                 and all(s in (1, 2) for s in self.strides[:self.num_stages]) and no_bn_training and conv_plan.CONV_MODE == "bf16x3")
 
-    def _forward_hip(self, img):
+    def _run_hip(self, img, P, n_frozen, keep=None):
+        """Plan ``P`` on images: stem, pooling, the blocks through ``run_block`` -- those below ``n_frozen`` under ``no_grad`` --
+        and the ``out_indices`` maps.  ``keep``: see ``run_block``; it receives the layers of the blocks from ``n_frozen`` on."""
         ops = ext.ops()
-        P = cached_plan(self, lambda: resnet_plan(self))
         N, _, Hi, Wi = img.shape
         st = P["stem"]
-        x = ops.conv2d_stem7_bf16x3(img.contiguous(), st.w_hi, st.w_lo, scale=st.scale, shift=st.shift, relu=True)
-        x, nhw = ops.maxpool2d_nhwc(x, (N, Hi // 2, Wi // 2))
-        outs = []
-        for i, blocks in enumerate(P["stages"]):
+        with torch.no_grad():
+            x = ops.conv2d_stem7_bf16x3(img.contiguous(), st.w_hi, st.w_lo, scale=st.scale, shift=st.shift, relu=True)
+            x, nhw = ops.maxpool2d_nhwc(x, (N, Hi // 2, Wi // 2))
+        outs, i = [], 0
+        for s, blocks in enumerate(P["stages"]):
             for B in blocks:
-                x, nhw = run_block(B, x, nhw)
-            if i in self.out_indices:
+                if i < n_frozen:
+                    with torch.no_grad():
+                        x, nhw = run_block(B, x, nhw)
+                else:
+                    x, nhw = run_block(B, x, nhw, keep)
+                i += 1
+            if s in self.out_indices:
                 outs.append(x.view(nhw[0], nhw[1], nhw[2], x.shape[1]).permute(0, 3, 1, 2))   # logical NCHW, channels-last memory
         return tuple(outs)
+
+    def _forward_hip(self, img):
+        return self._run_hip(img, cached_plan(self, lambda: resnet_plan(self)), len(self.blocks()))
 
     # ---- training with frozen norms: the eval lowering under autograd (DESIGN.md 4.12) ---------------------------------------
     def blocks(self):
@@ -309,49 +300,18 @@ class ResNet(BaseModule):
                 and conv_plan.CONV_MODE == "bf16x3" and conv_plan.train_products_ok()
                 and os.environ.get("SGC_BACKBONE_TRAIN_HIP", TRAIN_HIP_DEFAULT) != "0")
 
-    def _train_plan(self):
-        """The frozen prefix as eval plan entries and the folded (scale, shift) of every trainable layer.  Rebuilt when a
-        tensor of the prefix or of a norm changes -- not when a trainable weight does: those are read through
-        ``train_weight_planes()`` every step."""
-        blocks = self.blocks()
+    def _forward_hip_train(self, img, keep=None):
+        """The training forward on the kernels (see the module docstring): ``resnet_plan`` with the frozen prefix prepared and
+        every later layer a ``FrozenConv2d``.  The plan is rebuilt when a tensor of the prefix or of a norm changes -- not when
+        a trainable weight does: those are read through ``train_weight_planes()`` every step.  ``keep``: a list that receives
+        the output rows of every trainable layer in layer order (their signs are the ReLU gates of the backward)."""
         nf = self.frozen_prefix()
         norms = [m for m in self.modules() if isinstance(m, nn.modules.batchnorm._BatchNorm)]
-        watched = ([self.conv1.weight] + [t for b in blocks[:nf] for t in b.parameters()]
+        watched = ([self.conv1.weight] + [t for b in self.blocks()[:nf] for t in b.parameters()]
                    + [t for m in norms for t in list(m.parameters()) + list(m.buffers())])
         fp = (conv_plan.CONV_PRODUCTS, nf) + tuple((t.data_ptr(), t._version) for t in watched)
-
-        def build():
-            stem = Conv2dSpec(self.conv1, self.bn1, pad_in=False)
-            stem.set_weight(F.pad(stem.w.permute(1, 2, 0).reshape(64, 147), (0, 13)).contiguous())
-            train = [{name: tuple(t.contiguous() for t in conv_plan.fold_norm(conv.out_channels, bn, conv.bias, conv.weight.device))
-                      for name, (conv, bn) in _train_layers(b).items()} for b in blocks[nf:]]
-            return dict(stem=stem, frozen=[_block_specs(b) for b in blocks[:nf]], train=train)
-        return cached_plan(self, build, attr="_hip_train_plan", fingerprint=fp)
-
-    def _forward_hip_train(self, img, keep=None):
-        """The training forward on the kernels (see the module docstring).  ``keep``: a list that receives the output rows of
-        every trainable layer in layer order (their signs are the ReLU gates of the backward)."""
-        ops = ext.ops()
-        P = self._train_plan()
-        blocks = self.blocks()
-        nf = len(P["frozen"])
-        N, _, Hi, Wi = img.shape
-        with torch.no_grad():
-            st = P["stem"]
-            x = ops.conv2d_stem7_bf16x3(img.contiguous(), st.w_hi, st.w_lo, scale=st.scale, shift=st.shift, relu=True)
-            x, nhw = ops.maxpool2d_nhwc(x, (N, Hi // 2, Wi // 2))
-        outs, i = [], 0
-        for s, name in enumerate(self.res_layers):
-            for _ in getattr(self, name):
-                if i < nf:
-                    with torch.no_grad():
-                        x, nhw = run_block(P["frozen"][i], x, nhw)
-                else:
-                    x, nhw = run_block_train(blocks[i], P["train"][i - nf], x, nhw, keep)
-                i += 1
-            if s in self.out_indices:
-                outs.append(x.view(nhw[0], nhw[1], nhw[2], x.shape[1]).permute(0, 3, 1, 2))   # logical NCHW, channels-last memory
-        return tuple(outs)
+        P = cached_plan(self, lambda: resnet_plan(self, nf), attr="_hip_train_plan", fingerprint=fp)
+        return self._run_hip(img, P, nf, keep)
 
     def forward(self, x):
         """img [B*N, 3, H, W] -> the ``out_indices`` maps [B*N, C_l, H_l, W_l].  Eval mode on the GPU without autograd:

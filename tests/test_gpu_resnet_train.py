@@ -202,6 +202,37 @@ def test_function_refuses_relu_before_the_add_and_the_fp16_mode(gpu_ops, monkeyp
         FrozenNormConv2dFunction.apply(*args, False, True)
 
 
+# ---- 3b. the training layer IS the prepared layer --------------------------------------------------------------------------------
+@pytest.mark.parametrize("k,s,hw,kw", [(3, 1, (6, 7), dict()), (1, 1, (6, 7), dict(residual=True, relu=False, relu_after_add=True)),
+                                       (3, 2, (8, 8), dict()), (3, 2, (5, 7), dict()), (1, 2, (5, 7), dict(relu=False))])
+def test_frozen_conv2d_equals_conv2d_spec_bit_for_bit(gpu_ops, k, s, hw, kw):
+    """``FrozenConv2d`` (live weight, planes from ``sgc_pack_conv_weight``, under autograd) against ``Conv2dSpec`` (prepared
+    weight, planes from ``split_operand``) on one seeded convolution + eval BatchNorm: both go through ``conv2d_rows`` to the same
+    entry on the same hi / lo bits, so the rows are ``torch.equal``."""
+    from sgcdet_amd.plugin.conv_plan import Conv2dSpec, FrozenConv2d
+    g = torch.Generator().manual_seed(100 * k + 10 * s + hw[0])
+    conv, bn = nn.Conv2d(32, 32, k, stride=s, padding=k // 2, bias=False), nn.BatchNorm2d(32).eval()
+    with torch.no_grad():
+        conv.weight.copy_(torch.randn(conv.weight.shape, generator=g) / (k * 32 ** 0.5))
+        bn.weight.copy_(1.0 + 0.2 * torch.randn(32, generator=g))
+        bn.bias.copy_(0.1 * torch.randn(32, generator=g))
+        bn.running_mean.copy_(0.1 * torch.randn(32, generator=g))
+        bn.running_var.copy_(0.5 + torch.rand(32, generator=g))
+    conv, bn = conv.cuda(), bn.cuda()
+    nhw = (2,) + hw
+    onhw = (2, (hw[0] + s - 1) // s, (hw[1] + s - 1) // s)
+    x = torch.randn(nhw[0] * nhw[1] * nhw[2], 32, generator=g).cuda()
+    kw = dict(kw)
+    if kw.get("residual"):
+        kw["residual"] = torch.randn(onhw[0] * onhw[1] * onhw[2], 32, generator=g).cuda()
+    with torch.no_grad():
+        want, want_nhw = Conv2dSpec(conv, bn)(x, nhw, **kw)
+    got, got_nhw = FrozenConv2d(conv, bn)(x, nhw, **kw)
+    assert got_nhw == want_nhw == onhw and got.requires_grad and want.abs().max() > 0
+    print(f"FrozenConv2d vs Conv2dSpec k{k} s{s} {hw}: max difference {(got.detach() - want).abs().max().item():.3e}")
+    assert torch.equal(got.detach(), want)
+
+
 # ---- 4. the whole backbone -----------------------------------------------------------------------------------------------------
 class _NoLibraryLayers:
     """nn.Conv2d / nn.BatchNorm2d / nn.MaxPool2d forward raise while this is active."""
