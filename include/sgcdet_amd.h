@@ -534,8 +534,13 @@ int sgc_conv3d_cl_bf16x3_act(const float *x, const uint16_t *w_hi, const uint16_
  * are associated differently (tests bound the difference at 2e-5 of the tensor scale).
  *   wg_hi / wg_lo: bf16 hi / lo planes of the TRANSFORMED weights [4][9][Cout][Cin]: for the (dx, dy) tap t = dx*3 + dy and the z taps
  *   w0, w1, w2 of the module's weight: G[0][t] = w0, G[1][t] = (w0 + w1 + w2) / 2, G[2][t] = (w0 - w1 + w2) / 2, G[3][t] = w2.
- *   workspace: >= sgc_conv3d_winograd_z_workspace_floats() floats (the transform-domain input and output stacks).
- *   Supported (sgc_conv3d_winograd_z_supported): ix, iy >= 8, iz % 8 == 0, Cin % 32 == 0, Cout % 4 == 0, Cout > 64, 2 * ix * iy * iz >= 2048. */
+ *   workspace: >= sgc_conv3d_winograd_z_workspace_floats() = 2 * ix * iy * iz * Cout floats (the four transform-domain outputs).  A
+ *   stack of fewer than 2048 rows (iz == 4) runs a few workgroups per position; what the workspace holds BEYOND that size takes the
+ *   partial tiles of a split reduction -- as many splits as the plan asks for and k further multiples of the size hold, summed in
+ *   split order (deterministic, no atomics); with exactly the size the launch is unsplit.
+ *   Supported (sgc_conv3d_winograd_z_supported): ix, iy >= 8, Cin % 32 == 0, Cout % 4 == 0, Cout > 64, and iz == 4, or iz % 8 == 0 with
+ *   2 * ix * iy * iz >= 2048.  The transform-domain convolutions run in bricks of 4 images x 8 x 8 pixels or (iz == 4, and wherever it
+ *   issues fewer matrix rows: 20 x 20 slices) 2 images x 10 x 10 pixels; the result does not depend on the brick, bit for bit. */
 int sgc_conv3d_winograd_z_bf16x3(const float *x, const uint16_t *wg_hi, const uint16_t *wg_lo, const float *scale,
                                  const float *shift, const float *residual_or_null, float *y, int ix, int iy, int iz,
                                  int Cin, int Cout, int relu, float *workspace, int64_t workspace_floats, sgc_stream_t stream);

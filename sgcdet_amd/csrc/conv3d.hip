@@ -16,6 +16,9 @@ int g_conv_products = 3;     // NOT a tuning knob (it changes results; sgc_set_c
 //   halo_brick    round 3, interleaved A/B of the three shapes on the 40x40x16 and 80x80x32 layers (bit-identical results): 8x8x4 is
 //                 1.5 - 2.5 % faster than 4x4x16 (236 vs 241 us, 129.5 vs 133, 534 vs 546; 600 halo rows instead of 648) -> it is
 //                 the choice wherever it tiles the grid exactly
+//   wz_brick      Winograd-z stack, alternated with four scenes in flight (bit-identical results): 2 images x 10 x 10 on the three
+//                 20x20x8 layers 526.8 against 515.8 scenes/s for 4 x 8 x 8, +7 .. +11 in three jobs (profiles/r15_wz_bricks.md)
+//                 -> the brick with fewer matrix rows, 4 x 8 x 8 on a tie
 //   split_target  interleaved A/B, tools/split_ab.py: 128 / 256 are 20-30 % slower on the stride-2 and 400-voxel layers, 1024+ no better
 //   halo_narrow   1 = 64-column tiles for layers with <= 64 output channels and 32-column tiles (8 x 1 waves) for <= 32; 64 = never
 //                 below 64 columns (the round-2..4 form, A/B); 0 = always 128
@@ -289,14 +292,29 @@ static ConvPlan plan_conv(const ConvParams &p, int64_t OV, bool masked) {
   } else if (halo && !p.two_d && !masked && (small = halo_small_grid(p.gx, p.gy, p.gz, p.Cout)) != 0) {
     if (small == 1) brick(kConvHaloGrid, 10, 10, 4, 64);
     else brick(kConvHaloGrid, 6, 12, 4, 64);
-  } else if (halo && g_tune_halo_2d && p.two_d && p.M >= g_tune_halo_min_m && p.gy >= 8 && p.gz >= 8) {
+  } else if (halo && g_tune_halo_2d && p.two_d && p.wz_Z > 0 && p.gy >= 8 && p.gz >= 8) {
+    // The virtual Winograd stack of sgc_conv3d_winograd_z_bf16x3: 4 positions x J = Z / 2 images of gy x gz pixels, weight set = position.
+    // A brick's images belong to ONE position (the kernel derives the position and the transform from its first image), so the brick's
+    // image count must divide J: 4 images x 8 x 8 pixels for J % 4 == 0, 2 images x 10 x 10 pixels for J = 2 and J % 4 == 0 (J = 6 would
+    // fit the small brick, but no layer has it and nothing was measured there: it stays with the direct kernel).  Of the bricks that
+    // fit, the one that issues fewer matrix rows for the grid (both pad to 256 rows; 20 x 20 pixels: 8 bricks of 10 x 10 against 9 of
+    // 8 x 8 per two / four images); a tie keeps 4 x 8 x 8, so 40 x 40 and every grid it tiles exactly launch as they always have.
+    // A stack of J % 4 == 0 needs halo_min_m rows as before; the J = 2 stacks (10 x 10 x 4: 800 rows) are what the small brick is for.
+    const int J = p.wz_Z / 2;
+    const bool stack = !narrow_n && p.w_group_images == J && p.gx == 4 * J && p.wz_Z % 4 == 0;
+    const bool fit4 = stack && J % 4 == 0 && p.M >= g_tune_halo_min_m, fit2 = stack && (J == 2 || fit4);
+    const auto rows = [&p](int bx, int by, int bz) { return (int64_t)ceil_div(p.gx, bx) * ceil_div(p.gy, by) * ceil_div(p.gz, bz) * 256; };
+    const bool small = fit2 && (!fit4 || g_tune_wz_brick == 2 || (g_tune_wz_brick == 0 && rows(2, 10, 10) < rows(4, 8, 8)));
+    if (small) brick(kConvHaloWZ, 2, 10, 10, 128);
+    else if (fit4) brick(kConvHaloWZ, 4, 8, 8, 128);
+    if (pl.family == kConvHaloWZ && J % pl.bx != 0) pl.unsupported = "conv: a brick of the virtual Winograd stack must hold images of one position";
+    else if (pl.family != kConvHaloWZ) pl.unsupported = "conv: the virtual Winograd stack needs Z / 2 = 2 or a multiple of 4 (and then halo_min_m stack rows) and > 64 output channels";
+  } else if (halo && g_tune_halo_2d && p.two_d && p.wz_Z == 0 && p.M >= g_tune_halo_min_m && p.gy >= 8 && p.gz >= 8) {
     // 3 x 3 layers over a stack of images (the FPN's output convolutions): the 2-D form of the halo kernel, bricks of 16 x 16 pixels;
     // or bricks of 4 images x 8 x 8 pixels -- no halo along the image axis, 400 staged rows per 256 outputs: the geometry of the
-    // transform-domain convolutions of sgc_conv3d_winograd_z_bf16x3 (image groups = positions); halo_2d = 2 selects it for any stack
-    if (p.wz_Z > 0 && !narrow_n && p.w_group_images == p.wz_Z / 2 && p.w_group_images % 4 == 0 && p.gx == 2 * p.wz_Z)
-      brick(kConvHaloWZ, 4, 8, 8, 128);
-    else if (p.wz_Z > 0) pl.unsupported = "conv: the virtual Winograd stack needs Z / 2 a multiple of 4 and > 64 output channels";
-    else if ((g_tune_halo_2d == 2 || p.w_group_images > 0) && !narrow_n && p.gx % 4 == 0 && (p.w_group_images == 0 || p.w_group_images % 4 == 0))
+    // transform-domain convolutions of sgc_conv3d_winograd_z_bf16x3 (image groups = positions: the branch above); halo_2d = 2 selects
+    // it for any stack
+    if ((g_tune_halo_2d == 2 || p.w_group_images > 0) && !narrow_n && p.gx % 4 == 0 && (p.w_group_images == 0 || p.w_group_images % 4 == 0))
       brick(kConvHalo2D, 4, 8, 8, 128);
     else if (p.w_group_images > 0) pl.unsupported = "conv: grouped 2-D form needs groups of a multiple of 4 images and > 64 output channels";
     else brick(kConvHalo2D, 1, 16, 16, narrow_n ? 64 : 128);
@@ -309,6 +327,9 @@ static ConvPlan plan_conv(const ConvParams &p, int64_t OV, bool masked) {
     pl.splitk = pick_split_steps(p, ceil_div(p.M, BM), ceil_div(p.Cout, pl.bn), g_tune_split_target, &pl.steps_per);
   } else {
     pl.splitk = halo_splitk(ceil_div(p.gx, pl.bx) * ceil_div(p.gy, pl.by) * ceil_div(p.gz, pl.bz), ceil_div(p.Cout, pl.bn), p.Cin / BK);
+    // a Winograd stack of halo_min_m rows or more launches unsplit, as it always has (its per-layer A/B lines were taken that way, and
+    // with scenes in flight a split only adds CU-time); the few-brick launches of the small stacks split like every halo launch
+    if (pl.family == kConvHaloWZ && p.M >= g_tune_halo_min_m) pl.splitk = 1;
   }
   pl.ws_floats = pl.splitk > 1 ? (int64_t)pl.splitk * OV * p.Cout : 0;
   return pl;
@@ -388,7 +409,12 @@ static int conv3d_bf16x3(const float *x, const uint16_t *w_hi, const uint16_t *w
     return rows_gemm_launch(x, Cin, w_hi, w_lo, scale, shift, residual_or_null, y, nullptr, (int)OV, Cin, Cout, relu, 0, 0, 0, st);
   p.splitk = pl.splitk; p.steps_per = pl.steps_per;
   // the 2-D entry point carries no workspace: one split rather than float atomics (the result must not depend on the run)
-  if (p.two_d && !(p.ws && p.ws_floats >= pl.ws_floats)) p.splitk = 1;
+  // (the Winograd entry hands on what its caller gave beyond the transform-domain tensor: as many splits as that holds, none empty)
+  if (p.two_d && !(p.ws && p.ws_floats >= pl.ws_floats)) {
+    const int nchunks = Cin / BK, fit = p.ws ? (int)std::min<int64_t>(p.ws_floats / std::max<int64_t>(OV * Cout, 1), p.splitk) : 1;
+    const int per = ceil_div(nchunks, std::max(fit, 1));
+    p.splitk = ceil_div(nchunks, per);
+  }
   rc = conv_split_begin(p, OV, st);
   if (rc) return rc;
   if (pl.family == kConvTile) {
@@ -456,9 +482,9 @@ extern "C" int sgc_conv3d_cl_bf16x3_act(const float *x, const uint16_t *w_hi, co
 }
 
 extern "C" int sgc_conv3d_winograd_z_supported(int ix, int iy, int iz, int Cin, int Cout) {
-  // Z/2 images per position, in bricks of 4, more than 64 output channels; the rest is the 2-D halo gate of plan_conv on the virtual
-  // stack of 2 Z images of ix x iy pixels (slices of at least 8 x 8 pixels, halo_min_m rows in the stack)
-  if (ix <= 0 || iy <= 0 || iz < 8 || iz % 8 || Cin % 32 || Cout % 4 || Cout <= 64) return 0;
+  // Z/2 images per position, in bricks of 4 or 2, more than 64 output channels; the rest is plan_conv's gate of the virtual stack of
+  // 2 Z images of ix x iy pixels (slices of at least 8 x 8 pixels; Z = 4, or Z % 8 == 0 and halo_min_m rows in the stack)
+  if (ix <= 0 || iy <= 0 || iz < 4 || iz % 4 || Cin % 32 || Cout % 4 || Cout <= 64) return 0;
   ConvParams p = {};
   p.two_d = 1; p.w_group_images = iz / 2; p.wz_Z = iz;
   int ox, oy, oz;
@@ -479,7 +505,7 @@ extern "C" int sgc_conv3d_winograd_z_bf16x3(const float *x, const uint16_t *wg_h
                                             sgc_stream_t stream) {
   if (!x || !wg_hi || !wg_lo || !y || !workspace) return set_error(SGC_EINVAL, "sgc_conv3d_winograd_z_bf16x3: null pointer");
   if (!sgc_conv3d_winograd_z_supported(ix, iy, iz, Cin, Cout))
-    return set_error(SGC_EUNSUP, "sgc_conv3d_winograd_z_bf16x3: needs ix, iy >= 8, iz %% 8 == 0, Cin %% 32 == 0, Cout %% 4 == 0, Cout > 64, >= 2048 stack rows");
+    return set_error(SGC_EUNSUP, "sgc_conv3d_winograd_z_bf16x3: needs ix, iy >= 8, iz == 4 or iz %% 8 == 0 with >= 2048 stack rows, Cin %% 32 == 0, Cout %% 4 == 0, Cout > 64");
   if (workspace_floats < sgc_conv3d_winograd_z_workspace_floats(ix, iy, iz, Cin, Cout))
     return set_error(SGC_EINVAL, "sgc_conv3d_winograd_z_bf16x3: workspace too small");
   if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)workspace | (uintptr_t)residual_or_null | (uintptr_t)scale | (uintptr_t)shift) & 15)
@@ -491,8 +517,11 @@ extern "C" int sgc_conv3d_winograd_z_bf16x3(const float *x, const uint16_t *wg_h
   const int64_t n_out = V / 2 * (Cout / 4);
   // four 3 x 3 convolutions over (x, y) as ONE launch of the halo kernel's 2-D form on the VIRTUAL stack of 4 J images (the input
   // transform happens while the halo rows are staged: template flag WZ), weight set = image / J
-  int rc = conv3d_bf16x3(x, wg_hi, wg_lo, nullptr, nullptr, nullptr, m, 4 * J, ix, iy, Cin, Cout, 3, 1, 0, 0, nullptr, 0, nullptr, stream, 1,
-                         nullptr, 0, 0, J, iz);
+  // what the caller passed beyond the transform-domain tensor holds the partial tiles of a split reduction (the few-brick launches of
+  // the small stacks): summed in split order by conv_epilogue_kernel before the output transform reads m -- no atomics
+  const int64_t m_floats = 2 * V * Cout, spare = workspace_floats - m_floats;
+  int rc = conv3d_bf16x3(x, wg_hi, wg_lo, nullptr, nullptr, nullptr, m, 4 * J, ix, iy, Cin, Cout, 3, 1, 0, 0, spare > 0 ? m + m_floats : nullptr,
+                         spare > 0 ? spare : 0, nullptr, stream, 1, nullptr, 0, 0, J, iz);
   if (rc) return rc;
   hipLaunchKernelGGL(winograd_z_out_kernel, dim3((unsigned)std::min<int64_t>((n_out + 255) / 256, 65536)), dim3(256), 0, st,
                      reinterpret_cast<const float4 *>(m), reinterpret_cast<float4 *>(y), scale, shift,

@@ -24,7 +24,10 @@ namespace sgc {
 // z-pitch (in rows) of the halo image in LDS: the smallest pitch >= BZ + 2 for which every 32-row MFMA tile
 // of the brick holds each halo-row residue mod 16 exactly twice (checked offline for the three brick shapes:
 // 18 for BZ = 16, 12 for BZ = 8, 6 for BZ = 4) -- the precondition of the conflict-free lane assignment.
-__host__ __device__ constexpr int halo_pitch(int BZ) { return BZ == 8 ? 12 : BZ + 2; }
+// BZ = 10 (the 2 images x 10 x 10 Winograd brick, 200 rows + 56 pad rows) has no such pitch: tools/halo_pitch_enum.py replays the
+// kernel's greedy assignment for the pitches 12..16 and counts the 16-lane ds_read_b128 groups (of 16) that keep a two-way
+// conflict -- 13, 7, 12, 13, 12 -- so 13 it is; the LDS plan is the 139 KB epilogue tile at every one of them.
+__host__ __device__ constexpr int halo_pitch(int BZ) { return BZ == 8 ? 12 : BZ == 10 ? 13 : BZ + 2; }
 __host__ __device__ constexpr size_t halo_tab_offset(int lrows, int mrows = 256, int bnv = 128) {
   const size_t planes = (size_t)(2 * lrows + 2 * 2 * bnv) * LDKH * sizeof(uint16_t);   // A hi|lo + 2 x B hi|lo
   const size_t stage = (size_t)mrows * (bnv + 8) * sizeof(float);                      // epilogue tile [MROWS][BNV + 8]
@@ -35,6 +38,8 @@ __host__ __device__ constexpr size_t halo_tab_offset(int lrows, int mrows = 256,
 // otherwise spend three quarters of their matrix work on padding columns).
 // TD: 2-D form (sgc_conv2d_nhwc_bf16x3: the FPN's 3 x 3 output convolutions) -- the grid is (image, row, column),
 // a brick is BX images x BY x BZ pixels, there is no halo and no tap along x: 9 taps, (BY + 2)(BZ + 2) halo rows per image.
+// Bricks: 1 x 16 x 16 (324 halo rows) and 4 x 8 x 8 (400) of 256 pixels; 2 x 10 x 10 (288 halo rows, Winograd stack only) of 200 pixels
+// in 256 matrix rows -- the 20 x 20 and 10 x 10 slices of the neck, which 8 x 8 pixel bricks cover with 576 pixels for 400 / not at all.
 // STG: software-pipelined schedule with the barrier in the MIDDLE of a tap (round 4; the body explains the hazards).  The
 // lockstep form (STG = false) put the barrier at the end of a tap: behind it every wave first had to fetch the freshly published
 // weight fragments from LDS (MFMA pipe idle for an LDS round trip with 96 reads queued), and in front of it every wave waited
@@ -204,7 +209,7 @@ __global__ __launch_bounds__(512) void conv3d_halo_bf16x3_kernel(const ConvParam
     const bool in = row < HROWS && gx >= 0 && gx < p.ix && gy >= 0 && gy < p.iy && gz >= 0 && gz < p.iz;
     if constexpr (WZ) {
       // image gx = kpos * J + j: the two voxel rows of the raw volume [iy][iz][Z] whose combination is this transform row
-      const int J = p.wz_Z >> 1, kpos = X0 / J, j = gx - kpos * J;       // a brick's images belong to one position (J % BX == 0)
+      const int J = p.wz_Z >> 1, kpos = X0 / J, j = gx - kpos * J;       // a brick's images belong to one position (J % BX == 0: plan_conv checks it)
       const int za = kpos == 0 ? 2 * j - 1 : kpos == 2 ? 2 * j + 1 : 2 * j;
       const int zb = kpos <= 1 ? 2 * j + 1 : kpos == 2 ? 2 * j : 2 * j + 2;
       const unsigned col = (unsigned)((gy * p.iz + gz) * p.wz_Z);
@@ -526,12 +531,16 @@ template <int BX, int BY, int BZ, int BNV = 128, bool TD = false, bool WZ = fals
 static int launch_halo(ConvParamsB &p, hipStream_t st) {
   // the one-product modes and the Winograd stack: the software-pipelined form only.  (sgc_set_conv_products admits 1, 2 and 3 and
   // nothing else: any other value would select the pipelined NP = 3 form here, where the old ladder fell through to the lines below.)
-  if (g_conv_products != 3 || WZ)
-    return with_products(g_conv_products, [&](auto np) { return launch_halo_k<BX, BY, BZ, BNV, np(), TD, true, WZ>(p, st); });
-  // the lockstep form is kept for the fp32-faithful mode only: it is the reference of the schedule's bit-identity test, and the
-  // form of the whole-grid bricks (four row tiles per wave: the unrolled pipelined loop spills 600 registers there)
-  if (!g_tune_halo_stagger || BX * BY * BZ > 256) return launch_halo_k<BX, BY, BZ, BNV, 3, TD, false>(p, st);
-  return launch_halo_k<BX, BY, BZ, BNV, 3, TD, true>(p, st);
+  // (a Winograd brick has no direct twin: `if constexpr` keeps the two direct forms of its shape out of the library)
+  if constexpr (!WZ) {
+    if (g_conv_products == 3) {
+      // the lockstep form is kept for the fp32-faithful mode only: it is the reference of the schedule's bit-identity test, and the
+      // form of the whole-grid bricks (four row tiles per wave: the unrolled pipelined loop spills 600 registers there)
+      if (!g_tune_halo_stagger || BX * BY * BZ > 256) return launch_halo_k<BX, BY, BZ, BNV, 3, TD, false>(p, st);
+      return launch_halo_k<BX, BY, BZ, BNV, 3, TD, true>(p, st);
+    }
+  }
+  return with_products(g_conv_products, [&](auto np) { return launch_halo_k<BX, BY, BZ, BNV, np(), TD, true, WZ>(p, st); });
 }
 
 int launch_halo_z4(ConvParamsB &p, const ConvPlan &pl, hipStream_t st);   // conv3d_halo_z4.hip

@@ -34,6 +34,7 @@
   X("halo_small", g_tune_halo_small, 1, "1: whole-grid bricks for the 10x10x4 / 12x12x4 grids at Cout >= 512")               \
   X("halo_narrow", g_tune_halo_narrow, 1, "1: 64- and 32-column tiles for few output channels, 64: never below 64, 0: 128")  \
   X("halo_2d", g_tune_halo_2d, 1, "3x3 layers over an image stack: 1 bricks of 16 x 16 pixels, 2 of 4 images x 8 x 8, 0 tile kernel") \
+  X("wz_brick", g_tune_wz_brick, 0, "Winograd-z stack: 0 the brick with fewer matrix rows, 1: 4 images x 8 x 8, 2: 2 images x 10 x 10 (where each fits)") \
   X("halo_split_target", g_tune_halo_split_target, 192, "halo kernel: channel slices are split until a launch has this many workgroups") \
   X("halo_wave_fix", g_tune_halo_wave_fix, 1, "one more split on a small CU overflow: 1 latency geometry only, 2 always")    \
   X("split_target", g_tune_split_target, 512, "tile kernel: the reduction is split until a launch has this many workgroups") \

@@ -44,12 +44,17 @@ def set_conv_mode(mode):
 
 # Winograd F(2,3) along z for the wide 3x3x3 stride-1 layers (sgc_conv3d_winograd_z_bf16x3): 2/3 of the multiply-adds of
 # the layers that hold the chip at its power limit, at the price of a transform pass on either side.  "auto" = wherever the entry
-# point supports the shape (z extent a multiple of 8, x / y multiples of 8 so that the 8 x 8 pixel bricks tile the slices) and the
-# layer has at least WINOGRAD_Z_MIN_CH input channels; False = never.  Results differ from the direct kernel by summation order
+# point supports the shape (z extent a multiple of 8; the library tiles a slice with bricks of 8 x 8 or 10 x 10 pixels, whichever
+# issues fewer matrix rows: 40 x 40 takes the first, 20 x 20 the second) and the layer has at least WINOGRAD_Z_MIN_CH input
+# channels; False = never.  Results differ from the direct kernel by summation order
 # (<= 2e-5 of the tensor scale, tested); each choice is deterministic.  Set before the first forward: plans are cached.
 WINOGRAD_Z = {"0": False, "1": True}.get(os.environ.get("SGC_WINOGRAD_Z", ""), "auto")
 WINOGRAD_Z_MIN_CH = int(os.environ.get("SGC_WINOGRAD_Z_MIN_CH", "256"))
-WINOGRAD_Z_RAGGED = os.environ.get("SGC_WINOGRAD_Z_RAGGED", "1") != "0"     # also slices the 8 x 8 pixel bricks do not tile exactly (20 x 20)
+# the 10 x 10 x 4 scale (z extent 4: one 2-image x 10 x 10 brick per position, reduction split over the channel slices): opt-in, see
+# ConvSpec._winograd_planes and DESIGN.md 7.4 (per-layer A/B with four scenes in flight, profiles/r15_wz_bricks_layers_ab.txt: neither
+# 1024 -> 1024 nor 1024 -> 128 gains, so both keep the direct kernels by default)
+WINOGRAD_Z_Z4 = os.environ.get("SGC_WINOGRAD_Z_Z4", "0") == "1"
+WINOGRAD_Z_RAGGED = os.environ.get("SGC_WINOGRAD_Z_RAGGED", "1") != "0"     # also slices that are no multiple of 8 x 8 pixels (20 x 20: 10 x 10 bricks)
 # layers that keep the direct kernel although "auto" would give them the form: (Cin, Cout, gx, gy, gz) tuples, from per-layer A/B runs
 # with scenes in flight (profiles/r06_winograd_layers_ab.txt).  Env (A/B runs): SGC_WINOGRAD_Z_DENY="512:128:20:20:8,512:512:20:20:8"
 WINOGRAD_Z_DENY = {tuple(int(v) for v in item.split(":")) for item in os.environ.get("SGC_WINOGRAD_Z_DENY", "").split(",") if item}
@@ -106,12 +111,16 @@ class ConvSpec:
         self._wino = None                    # (g_hi, g_lo): transformed weight planes, built on first use
 
     def _winograd_planes(self, grid):
-        """The transformed weight planes when this call should take the Winograd-z form, else None."""
+        """The transformed weight planes when this call should take the Winograd-z form, else None.
+
+        Grids of z extent 4 (the 10 x 10 x 4 scale of config 2: 1024 -> 1024 and 1024 -> 128) pass only with ``WINOGRAD_Z_Z4`` and
+        where the library supports the shape.  Their transformed planes are larger than the direct ones: 1024 -> 1024 holds
+        4 x 9 x 1024^2 x 4 B = 151 MB (bf16 hi + lo) against 27 x 1024^2 x 4 B = 113 MB, built once per module."""
         if (WINOGRAD_Z is False or self.ksize != 3 or self.stride != 1 or self.transposed or CONV_MODE != "bf16x3"
                 or (WINOGRAD_Z == "auto" and self.cin_p < WINOGRAD_Z_MIN_CH)
                 or (not WINOGRAD_Z_RAGGED and (grid[0] % 8 or grid[1] % 8))):
             return None
-        if (self.cin_p, self.cout_p) + tuple(grid) in WINOGRAD_Z_DENY:
+        if (self.cin_p, self.cout_p) + tuple(grid) in WINOGRAD_Z_DENY or (grid[2] < 8 and not WINOGRAD_Z_Z4):
             return None
         ops = ext.ops()
         if not ops.conv3d_winograd_z_supported(grid, self.cin_p, self.cout_p):
@@ -120,7 +129,7 @@ class ConvSpec:
         # and no reduction split.  A layer ALONE needs enough of them to fill the chip (512 -> 128 @ 20x20x8: 36 workgroups, 154 us
         # against 55 us direct); with scenes in flight the other streams fill it and the saved multiply-adds count (+2 % at config 2).
         if WINOGRAD_Z == "auto" and not WINOGRAD_IN_FLIGHT:
-            wgs = (grid[2] // 8) * -(-grid[0] // 8) * -(-grid[1] // 8) * 4 * -(-self.cout_p // 128)
+            wgs = -(-grid[2] // 8) * -(-grid[0] // 8) * -(-grid[1] // 8) * 4 * -(-self.cout_p // 128)
             if wgs < 192:
                 return None
         if self._wino is None:

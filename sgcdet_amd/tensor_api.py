@@ -667,6 +667,8 @@ class TensorOps:
         g = torch.stack([w[:, 0], (w[:, 0] + w[:, 1] + w[:, 2]) / 2, (w[:, 0] - w[:, 1] + w[:, 2]) / 2, w[:, 2]])
         return g.float().contiguous()
 
+    WINOGRAD_Z_MAX_SPLITS = 8      # the entry point splits as far as its plan says AND the workspace beyond 2 V Cout floats holds
+
     def conv3d_winograd_z_supported(self, grid, Cin, Cout):
         return bool(self.lib._dll.sgc_conv3d_winograd_z_supported(int(grid[0]), int(grid[1]), int(grid[2]), int(Cin), int(Cout)))
 
@@ -687,6 +689,8 @@ class TensorOps:
         if y.shape != (V, Cout) or (residual is not None and residual.shape != y.shape):
             raise RuntimeError("conv3d_winograd_z: bad `out` / residual shape")
         n = int(self.lib._dll.sgc_conv3d_winograd_z_workspace_floats(ix, iy, iz, Cin, Cout))
+        if iz == 4:          # a small stack (a few bricks per position): room for the partial tiles of up to 8 reduction splits
+            n *= 1 + self.WINOGRAD_Z_MAX_SPLITS
         ws = torch.empty(max(n, 4), dtype=torch.float32, device=x.device)
         self._call("sgc_conv3d_winograd_z_bf16x3", x, g_hi, g_lo, scale, shift, residual, y, ix, iy, iz, Cin, Cout, int(relu), ws, n,
                    _meta=dict(V=V, Cin=Cin, Cout=Cout, taps=27, OV=V, mac_frac=2.0 / 3.0))
