@@ -185,6 +185,36 @@ int64_t sgc_conv2d_wgrad_workspace_floats(int N, int H, int W, int Cin, int Cout
 int sgc_frozen_norm_act_backward(const float *dy, const float *y_or_null, const float *scale_or_null, float *g, float *gres_or_null,
                                  int64_t rows, int C, int relu, sgc_stream_t stream);
 
+/* ------------------------------------------------------------------------- *
+ * 13. Training the image FPN: the top-down step and the bias gradient (csrc/fpn_train.hip)
+ * ------------------------------------------------------------------------- */
+
+/* Top-down step of the FPN on channels-last maps: nearest upsampling of the coarse map to the fine map's size, added to it.
+ *   out[n][h][w][:] = fine[n][h][w][:] + coarse[n][ih(h)][iw(w)][:],  ih(h) = min(h * Hs / Hd, Hs - 1) in integers, iw likewise
+ *   fine, out [N, Hd, Wd, C], coarse [N, Hs, Ws, C];  out may be fine itself (the in-place form).
+ * The index rule equals F.interpolate(mode = "nearest") for Hs in {ceil(Hd / 2), floor(Hd / 2)} (what a stride-2 stage produces);
+ * any 1 <= Hs <= Hd, 1 <= Ws <= Wd is accepted.  Needs C % 4 == 0 and 16-byte aligned pointers (SGC_EUNSUP otherwise). */
+int sgc_upsample_nearest_add_nhwc(const float *fine, const float *coarse, float *out, int N, int Hd, int Wd, int Hs, int Ws, int C,
+                                  sgc_stream_t stream);
+
+/* Its gradient with respect to the coarse map (the fine map's gradient is gout itself):
+ *   gcoarse[n][hs][ws][:] = sum of gout[n][h][w][:] over h in [ceil(hs * Hd / Hs), ceil((hs + 1) * Hd / Hs)) below Hd, w likewise
+ * -- the pixels whose ih / iw is (hs, ws); at most 2 x 2 of them for Hs = ceil(Hd / 2), 3 x 3 for the floor of an odd size.  One thread owns an output
+ * element and adds h outer, w inner: no atomics, the same bits on every run; every element of gcoarse is written.
+ * Same requirements as the forward. */
+int sgc_upsample_nearest_add_backward_nhwc(const float *gout, float *gcoarse, int N, int Hd, int Wd, int Hs, int Ws, int C,
+                                           sgc_stream_t stream);
+
+/* out[c] = sum over r of x[r][c], x [rows, C] dense: the bias gradient of a convolution on rows.  Two stages in a fixed order --
+ * per-workgroup partial sums of a row range into the workspace, then one workgroup adds the partial sums in index order -- so two
+ * runs give the same bits, and no value passes through more than 160 dependent fp32 additions on its way into out[c] (75 at
+ * rows = 192 000, C = 256): |out[c] - exact| <= 160 * 2^-24 * sum over r of |x[r][c]| to first order.
+ * sgc_rows_colsum_workspace_floats(rows, C): the floats the workspace needs; 0: one workgroup row covers the input and writes
+ * out directly (the workspace may be null); -1: a shape the entry refuses (C % 4 != 0, rows < 1, or so many rows -- beyond
+ * about 600 000 -- that the chain bound would not hold).  16-byte aligned pointers; SGC_EUNSUP / SGC_EINVAL before any launch. */
+int sgc_rows_colsum(const float *x, float *out, int64_t rows, int C, float *workspace, int64_t workspace_floats, sgc_stream_t stream);
+int64_t sgc_rows_colsum_workspace_floats(int64_t rows, int C);
+
 #ifdef __cplusplus
 }
 #endif

@@ -111,6 +111,9 @@ TRAIN_SIGNATURES = {
     "sgc_head_loss_scale_grads": [_p, _p, _p] + [_i] * 3 + [_p] * 5,
     "sgc_conv2d_wgrad_bf16x3": [_p] * 3 + [_i] * 7 + [_p, C.c_int64] + [_p],
     "sgc_frozen_norm_act_backward": [_p] * 5 + [C.c_int64, _i, _i] + [_p],
+    "sgc_upsample_nearest_add_nhwc": [_p] * 3 + [_i] * 6 + [_p],
+    "sgc_upsample_nearest_add_backward_nhwc": [_p] * 2 + [_i] * 6 + [_p],
+    "sgc_rows_colsum": [_p, _p, C.c_int64, _i, _p, C.c_int64] + [_p],
 }
 
 TRAIN_INTROSPECTION = {
@@ -118,6 +121,7 @@ TRAIN_INTROSPECTION = {
     "sgc_grad_sqnorm_batch_workspace_bytes": (C.c_int64, [_i]),
     "sgc_head_loss_workspace_bytes": (C.c_int64, [_i] * 2),
     "sgc_conv2d_wgrad_workspace_floats": (C.c_int64, [_i] * 7),
+    "sgc_rows_colsum_workspace_floats": (C.c_int64, [C.c_int64, _i]),
 }
 
 # include/sgcdet_amd_image.h: the 2-D convolutions of the image-side CNNs (no CPU-oracle twin)

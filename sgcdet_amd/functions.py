@@ -438,10 +438,15 @@ class FrozenNormConv2dFunction(Function):
       transposed form of ``sgc_conv2d_nhwc_ex_bf16x3`` (sums by output parity, 2.25 taps per pixel), cropped to H x W when a
       side is odd; 1x1 stride 2 -- the 1x1 GEMM on g, written to the even positions of a zeroed map;
     * weight gradient: ``sgc_conv2d_wgrad_bf16x3``.
-    x, y and the weight are saved; a layer's y is the next layer's x, so nothing is kept twice."""
+    x, y and the weight are saved; a layer's y is the next layer's x, so nothing is kept twice.
+
+    A tenth argument ``bias`` [Cout] makes it ``conv(x) + bias`` with a TRAINABLE bias (the FPN's convolutions: no norm, no
+    activation -- DESIGN.md 4.13): it takes the place of ``shift`` in the epilogue (``scale``, ``shift`` and both ReLU flags must
+    be None / False), and the backward adds its gradient, the column sums of dy (``sgc_rows_colsum``).
+    ``conv_plan.BiasConv2d`` wraps this form."""
 
     @staticmethod
-    def forward(ctx, x, weight, scale, shift, residual, nhw, stride, relu, relu_after_add):
+    def forward(ctx, x, weight, scale, shift, residual, nhw, stride, relu, relu_after_add, bias=None):
         from .plugin.conv_plan import conv2d_rows
         _require_bf16_planes("FrozenNormConv2dFunction")
         cout, cin, k = weight.shape[0], weight.shape[1], weight.shape[2]
@@ -452,6 +457,10 @@ class FrozenNormConv2dFunction(Function):
                                "use relu_after_add (the ReLU behind the skip addition)")
         if relu and relu_after_add:
             raise RuntimeError("FrozenNormConv2dFunction: relu and relu_after_add exclude each other")
+        if bias is not None:
+            if scale is not None or shift is not None or relu or relu_after_add or bias.shape != (cout,):
+                raise RuntimeError("FrozenNormConv2dFunction: a trainable bias [Cout] comes without scale / shift and without a ReLU")
+            shift = bias
         hi, lo = _TRAIN_PLANES.get(weight)                     # [k*k, Cout, Cin]
         x = x.float().contiguous()
         res = None if residual is None else residual.detach().float().contiguous()
@@ -460,6 +469,7 @@ class FrozenNormConv2dFunction(Function):
         y = conv2d_rows(x, hi, lo, nhw, k, stride, scale=scale, shift=shift, residual=res, relu=relu, relu_after_add=relu_after_add)
         ctx.save_for_backward(x, y, weight, scale)
         ctx.geom = (tuple(nhw), k, stride, bool(relu or relu_after_add), residual is not None)
+        ctx.has_bias = bias is not None
         return y
 
     @staticmethod
@@ -497,7 +507,30 @@ class FrozenNormConv2dFunction(Function):
         if ctx.needs_input_grad[1]:
             dwk = ops.conv2d_wgrad_bf16x3(x, g, (N, H, W), k, stride)               # [k*k, Cout, Cin]
             dw = ops.unpack_conv_wgrad(dwk, weight.shape).to(weight.dtype)
-        return dx, dw, None, None, gres, None, None, None, None
+        if not ctx.has_bias:
+            return dx, dw, None, None, gres, None, None, None, None
+        db = ops.rows_colsum(g).to(weight.dtype) if ctx.needs_input_grad[9] else None       # g is dy: no gate, no scale
+        return dx, dw, None, None, gres, None, None, None, None, db
+
+
+class UpsampleNearestAddFunction(Function):
+    """The FPN's top-down step on channels-last rows: ``fine + nearest_upsample(coarse)`` to the fine map's size,
+    forward ``sgc_upsample_nearest_add_nhwc`` (out of place), backward ``sgc_upsample_nearest_add_backward_nhwc`` for the coarse
+    rows; the fine rows' gradient is dy itself.  ``apply(fine_rows [N*Hd*Wd, C], coarse_rows [N*Hs*Ws, C], (N, Hd, Wd),
+    (N, Hs, Ws))``.  Saves nothing."""
+
+    @staticmethod
+    def forward(ctx, fine, coarse, dims_fine, dims_coarse):
+        ctx.dims = (tuple(dims_fine), tuple(dims_coarse))
+        return ext.ops().upsample_nearest_add_nhwc(fine.detach().float().contiguous(), coarse.detach().float().contiguous(),
+                                                   *ctx.dims)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        dy = dy.float().contiguous()
+        gcoarse = ext.ops().upsample_nearest_add_backward_nhwc(dy, *ctx.dims) if ctx.needs_input_grad[1] else None
+        return (dy if ctx.needs_input_grad[0] else None), gcoarse, None, None
 
 
 class ChannelsLastConvTranspose3dFunction(Function):

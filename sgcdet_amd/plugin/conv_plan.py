@@ -3,8 +3,8 @@
 ``ConvSpec`` (3-D: neck and head, ``sgc_conv3d_cl_*`` / Winograd-z), ``Conv2dSpec`` (2-D: backbone, FPN and depth net),
 ``LinearSpec`` and ``BlockDiagSpec`` (the row GEMMs of the transformer) each hold one layer as the kernels take it and dispatch
 it in ``__call__``.  ``conv2d_rows`` is the one rule that sends a 2-D layer to ``sgc_conv2d_nhwc_bf16x3`` /
-``sgc_conv2d_nhwc_ex_bf16x3`` / ``sgc_conv2d_nhwc_strided_bf16x3``: ``Conv2dSpec`` and its training twin ``FrozenConv2d`` (frozen
-norm, autograd) both reach the entries through it, so the training forward is the eval forward.  Eval BatchNorm (running statistics)
+``sgc_conv2d_nhwc_ex_bf16x3`` / ``sgc_conv2d_nhwc_strided_bf16x3``: ``Conv2dSpec`` and its training twins ``FrozenConv2d`` (frozen
+norm, autograd) and ``BiasConv2d`` (no norm, trainable bias) all reach the entries through it, so the training forward is the eval forward.  Eval BatchNorm (running statistics)
 and the bias are folded into a per-channel scale / shift for the kernel's epilogue (``fold_norm``, the only copy), weights are
 permuted once to ``[tap][Cout][Cin]``, and channel counts are zero-padded to multiples of 32 (the K tile; ``_pad_to``) with zero
 weight rows, scale 1 and shift 0, so padded output columns are exactly 0.  ``cached_plan`` keeps a module's plan and rebuilds it
@@ -234,6 +234,24 @@ class FrozenConv2d:
         s = self.conv.stride[0]
         y = FrozenNormConv2dFunction.apply(x, self.conv.weight, self.scale, self.shift, residual, nhw, s, relu, relu_after_add)
         return y, (nhw[0], (nhw[1] + s - 1) // s, (nhw[2] + s - 1) // s)
+
+
+class BiasConv2d:
+    """``FrozenConv2d``'s sibling for a convolution WITHOUT a norm whose bias trains (the image FPN): stride 1,
+    no activation.  Weight and bias are the module's parameters, read live at every call -- the weight through
+    ``train_weight_planes()``, the bias as the epilogue's shift -- and both get gradients from ``FrozenNormConv2dFunction``."""
+
+    def __init__(self, conv):
+        if conv.bias is None or conv.stride[0] != 1:
+            raise ValueError("BiasConv2d: a stride-1 convolution with a bias")
+        self.conv = conv
+
+    def __call__(self, x, nhw, residual=None, relu=False, relu_after_add=False):
+        from ..functions import FrozenNormConv2dFunction
+        if relu or relu_after_add:
+            raise NotImplementedError("BiasConv2d: no activation (its gate would have to be saved)")
+        y = FrozenNormConv2dFunction.apply(x, self.conv.weight, None, None, residual, nhw, 1, False, False, self.conv.bias)
+        return y, tuple(nhw)
 
 
 # training / autograd path of the neck and head convolutions: "hip" = forward, input and weight gradients on the MFMA

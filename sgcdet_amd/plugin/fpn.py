@@ -14,13 +14,24 @@ channels-last rows and returns [N, C, H, W] tensors that ARE channels-last in me
 [N, H, W, C] result): `SGCDet.forward_features` reads them in place, the NCHW -> NHWC pass of the path disappears, and
 nothing else changes for the caller.  Backbone maps that arrive channels-last in memory are read in place too; NCHW ones
 are transposed once by ``sgc_nchw_to_nhwc_crop``.
+
+Under autograd on the GPU (``_train_hip_ok``) the same walk runs with every convolution a ``conv_plan.BiasConv2d``
+(``functions.FrozenNormConv2dFunction`` with a trainable bias: forward, input, weight and bias gradients on the HIP kernels) and
+the top-down step a ``functions.UpsampleNearestAddFunction``; the outputs have the eval path's layout and bits.
+``SGC_FPN_TRAIN_HIP=0`` keeps the torch formulation.
 """
+import os
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .. import ext
 from ..mmcv_lite import NECKS
-from .conv_plan import Conv2dSpec, cached_plan, image_rows
+from . import conv_plan
+from .conv_plan import BiasConv2d, Conv2dSpec, cached_plan, image_rows
+
+TRAIN_HIP_DEFAULT = "1"      # SGC_FPN_TRAIN_HIP when the environment does not set it (DESIGN.md 4.13 says how it was chosen)
 
 
 class _ConvModule(nn.Module):
@@ -74,36 +85,70 @@ class FPN(nn.Module):
         return tuple(outs)
 
     # ---- MFMA kernels on channels-last rows ----------------------------------------------------------------------
-    def _build_plan(self):
-        def spec(m):                          # bias only: no norm to fold, channel counts are multiples of 32 (``forward``)
-            return Conv2dSpec(m.conv, pad_in=False, pad_out=False, unit_scale=False)
-        return [spec(m) for m in self.lateral_convs], [spec(m) for m in self.fpn_convs]
+    def _build_plan(self, make=None):
+        """The layers as the walker calls them: ``Conv2dSpec`` (eval: bias only, no norm to fold; channel counts are multiples
+        of 32, see ``forward``) or ``make(conv)`` (training: ``BiasConv2d``)."""
+        if make is None:
+            def make(conv):
+                return Conv2dSpec(conv, pad_in=False, pad_out=False, unit_scale=False)
+        return [make(m.conv) for m in self.lateral_convs], [make(m.conv) for m in self.fpn_convs]
 
-    def _forward_hip(self, inputs):
-        lat_specs, out_specs = cached_plan(self, self._build_plan)
+    @staticmethod
+    def _top_down(fine, coarse, dims_fine, dims_coarse, train):
+        """Nearest upsample of ``coarse`` to the finer size, added to ``fine``: in place without autograd, the Function with it."""
+        if train:
+            from ..functions import UpsampleNearestAddFunction
+            return UpsampleNearestAddFunction.apply(fine, coarse, dims_fine, dims_coarse)
+        return ext.ops().upsample_nearest_add_nhwc(fine, coarse, dims_fine, dims_coarse, out=fine)
+
+    def _forward_hip(self, inputs, train=False):
+        """THE walk over the layers, in eval and in training alike.  ``train``: the layers are ``BiasConv2d``s (the parameters
+        are read live, so that plan never goes stale) and the inputs become rows under autograd -- a view of a map that is
+        channels-last in memory, the copy torch makes of an NCHW-contiguous one."""
+        if train:
+            lat_layers, out_layers = cached_plan(self, lambda: self._build_plan(BiasConv2d), attr="_hip_train_plan", fingerprint=())
+        else:
+            lat_layers, out_layers = cached_plan(self, self._build_plan)
         lat, dims = [], []
-        for i, spec in enumerate(lat_specs):
-            rows, nhw = image_rows(inputs[i + self.start_level])
-            lat.append(spec(rows, nhw, relu=False)[0])
+        for i, layer in enumerate(lat_layers):
+            x = inputs[i + self.start_level]
+            if train:
+                N, Cin, H, W = x.shape
+                rows, nhw = x.permute(0, 2, 3, 1).reshape(N * H * W, Cin), (N, H, W)
+            else:
+                rows, nhw = image_rows(x)
+            lat.append(layer(rows, nhw, relu=False)[0])
             dims.append(nhw)
         C = self.out_channels
-        for i in range(len(lat) - 1, 0, -1):                 # top-down: nearest upsample to the finer size, add in place
-            (N, Hs, Ws), (_, Hd, Wd) = dims[i], dims[i - 1]
-            src = lat[i].view(N, Hs, Ws, C)
-            ih, iw = _nearest_index(Hd, Hs, src.device), _nearest_index(Wd, Ws, src.device)
-            lat[i - 1].view(N, Hd, Wd, C).add_(src[:, ih][:, :, iw])
+        for i in range(len(lat) - 1, 0, -1):
+            lat[i - 1] = self._top_down(lat[i - 1], lat[i], dims[i - 1], dims[i], train)
         outs = []
-        for i, spec in enumerate(out_specs):
+        for i, layer in enumerate(out_layers):
             N, H, W = dims[i]
-            y, _ = spec(lat[i], dims[i], relu=False)
+            y, _ = layer(lat[i], dims[i], relu=False)
             outs.append(y.view(N, H, W, C).permute(0, 3, 1, 2))          # logical NCHW, channels-last memory
         while len(outs) < self.num_outs:
             outs.append(outs[-1][:, :, ::2, ::2])
         return tuple(outs)
 
+    def _channels_ok(self):
+        return all(c % 32 == 0 for c in self.in_channels) and self.out_channels % 32 == 0
+
+    def _train_hip_ok(self, inputs):
+        """Does this call train on the HIP kernels (DESIGN.md 4.13)?  Autograd is recording and something here wants a gradient;
+        the maps the module reads are CUDA float32; every channel count is a multiple of 32; the weight planes' arithmetic mode
+        (not fp16); and the environment switch."""
+        used = inputs[self.start_level:self.backbone_end_level]
+        return (torch.is_grad_enabled()
+                and (any(x.requires_grad for x in used) or any(p.requires_grad for p in self.parameters()))
+                and all(x.is_cuda and x.dtype == torch.float32 for x in used) and self._channels_ok()
+                and conv_plan.CONV_MODE == "bf16x3" and conv_plan.train_products_ok()
+                and os.environ.get("SGC_FPN_TRAIN_HIP", TRAIN_HIP_DEFAULT) != "0")
+
     def forward(self, inputs):
         x0 = inputs[0]
-        if (not self.training and not torch.is_grad_enabled() and x0.is_cuda
-                and all(c % 32 == 0 for c in self.in_channels) and self.out_channels % 32 == 0):
+        if self._train_hip_ok(inputs):
+            return self._forward_hip(inputs, train=True)
+        if not self.training and not torch.is_grad_enabled() and x0.is_cuda and self._channels_ok():
             return self._forward_hip(inputs)
         return self._forward_torch(inputs)

@@ -1194,6 +1194,54 @@ class TensorOps:
             self._call("sgc_frozen_norm_act_backward", dy, y if relu else None, scale, g, gres, dy.shape[0], dy.shape[1], int(bool(relu)))
         return g, gres
 
+    def upsample_nearest_add_nhwc(self, fine, coarse, dims_fine, dims_coarse, out=None):
+        """Top-down step of the FPN on rows (``sgc_upsample_nearest_add_nhwc``): fine [N*Hd*Wd, C] + the nearest upsampling of
+        coarse [N*Hs*Ws, C] to Hd x Wd.  ``out``: None (a new tensor) or ``fine`` itself (in place)."""
+        self._check(fine=fine, coarse=coarse)
+        self._f32(fine=fine, coarse=coarse)
+        (N, Hd, Wd), (Ns, Hs, Ws) = dims_fine, dims_coarse
+        if (fine.dim() != 2 or coarse.dim() != 2 or N != Ns or fine.shape[0] != N * Hd * Wd or coarse.shape[0] != N * Hs * Ws
+                or fine.shape[1] != coarse.shape[1]):
+            raise RuntimeError("upsample_nearest_add_nhwc: inconsistent shapes")
+        if out is None:
+            out = torch.empty_like(fine)
+        elif out is not fine:
+            raise RuntimeError("upsample_nearest_add_nhwc: out is a new tensor or fine itself")
+        self._call("sgc_upsample_nearest_add_nhwc", fine, coarse, out, N, Hd, Wd, Hs, Ws, fine.shape[1])
+        return out
+
+    def upsample_nearest_add_backward_nhwc(self, gout, dims_fine, dims_coarse):
+        """Gradient of ``upsample_nearest_add_nhwc`` with respect to the coarse rows: gout [N*Hd*Wd, C] -> [N*Hs*Ws, C]
+        (``sgc_upsample_nearest_add_backward_nhwc``); the fine rows' gradient is gout itself."""
+        self._check(gout=gout)
+        self._f32(gout=gout)
+        (N, Hd, Wd), (Ns, Hs, Ws) = dims_fine, dims_coarse
+        if gout.dim() != 2 or N != Ns or gout.shape[0] != N * Hd * Wd:
+            raise RuntimeError("upsample_nearest_add_backward_nhwc: inconsistent shapes")
+        gcoarse = torch.empty((N * Hs * Ws, gout.shape[1]), dtype=torch.float32, device=gout.device)
+        self._call("sgc_upsample_nearest_add_backward_nhwc", gout, gcoarse, N, Hd, Wd, Hs, Ws, gout.shape[1])
+        return gcoarse
+
+    def rows_colsum_workspace_floats(self, rows, C):
+        """Floats of the workspace ``rows_colsum`` sums its partial results through; 0: one workgroup row covers the input."""
+        n = int(self.lib._dll.sgc_rows_colsum_workspace_floats(rows, C))
+        if n < 0:
+            raise RuntimeError("rows_colsum: " + self.lib.last_error())
+        return n
+
+    def rows_colsum(self, x):
+        """x [rows, C] -> [C], the column sums in a fixed order (``sgc_rows_colsum``): a convolution's bias gradient."""
+        self._check(x=x)
+        self._f32(x=x)
+        if x.dim() != 2:
+            raise RuntimeError("rows_colsum: expects [rows, C]")
+        rows, Cc = x.shape
+        n = self.rows_colsum_workspace_floats(rows, Cc)
+        ws = torch.empty(n, dtype=torch.float32, device=x.device) if n > 0 else None
+        out = torch.empty(Cc, dtype=torch.float32, device=x.device)
+        self._call("sgc_rows_colsum", x, out, rows, Cc, ws, n)
+        return out
+
     def _conv_workspace(self, device, ix, iy, iz, Cin, Cout, ksize, stride, transposed, bf16x3):
         """Split-K layers get a workspace so that their partial sums are added in a fixed order (bit-identical
         results from run to run); (None, 0) for layers that are not split."""
