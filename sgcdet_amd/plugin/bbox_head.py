@@ -74,11 +74,14 @@ class ImVoxelHeadV2(nn.Module):
         normal_init(self.reg_conv, std=0.01)
         normal_init(self.cls_conv, std=0.01, bias=bias_init_with_prob(0.01))
 
-    def _build_plan(self):
-        """The three 3x3x3 convolutions share their input: one fused conv with
-        Cout = 1 + n_reg + n_classes (centerness | reg | cls) on the MFMA kernel."""
+    def _fused_weight(self):
+        """The three 3x3x3 convolutions share their input: one convolution with Cout = 1 + n_reg + n_classes
+        (centerness | reg | cls) -> (its weight, n_reg)."""
         w = torch.cat([self.centerness_conv.weight, self.reg_conv.weight, self.cls_conv.weight], 0)
-        n_reg = self.reg_conv.weight.shape[0]
+        return w, self.reg_conv.weight.shape[0]
+
+    def _build_plan(self):
+        w, n_reg = self._fused_weight()
         bias = torch.cat([self.cls_conv.bias.new_zeros(1 + n_reg), self.cls_conv.bias])
         return ConvSpec(w, None, bias=bias, ksize=3, pad_out=False), n_reg
 
@@ -109,10 +112,10 @@ class ImVoxelHeadV2(nn.Module):
     def _forward_autograd_hip(self, feats):
         """Training / autograd path on the HIP kernels: the three 3x3x3 convolutions of a scale as ONE convolution with the
         concatenated weights (autograd splits the weight gradient back), imvoxel_head_v2.py:75-78,103-110."""
+        # not one walker with _forward_hip: there a folded bias and exp in the kernel's epilogue, here torch ops and an ephemeral plane
         from ..functions import ChannelsLastConv3dFunction, train_weight_planes
-        w = torch.cat([self.centerness_conv.weight, self.reg_conv.weight, self.cls_conv.weight], 0)
+        w, n_reg = self._fused_weight()
         train_weight_planes().mark_ephemeral(w)          # a fresh temporary every step: packed per use (once for the three scales), never registered
-        n_reg = self.reg_conv.weight.shape[0]
         ctr, reg, cls = [], [], []
         for x, scale in zip(feats, self.scales):
             rows, grid = to_channels_last_rows(x)

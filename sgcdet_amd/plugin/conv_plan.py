@@ -4,7 +4,9 @@
 ``LinearSpec`` and ``BlockDiagSpec`` (the row GEMMs of the transformer) each hold one layer as the kernels take it and dispatch
 it in ``__call__``.  ``conv2d_rows`` is the one rule that sends a 2-D layer to ``sgc_conv2d_nhwc_bf16x3`` /
 ``sgc_conv2d_nhwc_ex_bf16x3`` / ``sgc_conv2d_nhwc_strided_bf16x3``: ``Conv2dSpec`` and its training twins ``FrozenConv2d`` (frozen
-norm, autograd) and ``BiasConv2d`` (no norm, trainable bias) all reach the entries through it, so the training forward is the eval forward.  Eval BatchNorm (running statistics)
+norm, autograd) and ``BiasConv2d`` (no norm, trainable bias) all reach the entries through it, so the training forward is the eval forward.
+``TrainConv3d`` is ``ConvSpec``'s training twin (convolution Function + ``bn_rows`` with a live norm and the fused tail): both are built
+by ``make(conv, bn)`` (``conv_spec`` for eval), so the neck walks one plan in either mode.  Eval BatchNorm (running statistics)
 and the bias are folded into a per-channel scale / shift for the kernel's epilogue (``fold_norm``, the only copy), weights are
 permuted once to ``[tap][Cout][Cin]``, and channel counts are zero-padded to multiples of 32 (the K tile; ``_pad_to``) with zero
 weight rows, scale 1 and shift 0, so padded output columns are exactly 0.  ``cached_plan`` keeps a module's plan and rebuilds it
@@ -150,6 +152,13 @@ class ConvSpec:
             raise NotImplementedError("the output activation lives in the bf16x3 convolution's epilogue")
         return ext.ops().conv3d_cl(x, self.wt, grid, self.ksize, self.stride, self.transposed, self.scale,
                                    self.shift, residual, relu)
+
+
+def conv_spec(conv, bn=None):
+    """``ConvSpec`` of an ``nn.Conv3d`` / ``nn.ConvTranspose3d`` module and the norm behind it: kernel size, stride, form and bias
+    are the module's, so the eval layer and its training twin ``TrainConv3d`` are both built by ``make(conv, bn)``."""
+    return ConvSpec(conv.weight, bn, bias=conv.bias, ksize=conv.kernel_size[0], stride=conv.stride[0],
+                    transposed=isinstance(conv, torch.nn.ConvTranspose3d))
 
 
 class Conv2dSpec:
@@ -313,22 +322,6 @@ def train_products_ok():
     return CONV_PRODUCTS != 2
 
 
-def conv_rows(conv, rows, grid):
-    """``nn.Conv3d`` module (k in {1,3}, padding k//2) applied to channels-last rows with autograd on the HIP kernels."""
-    from ..functions import ChannelsLastConv3dFunction
-    k, s = conv.kernel_size[0], conv.stride[0]
-    y = ChannelsLastConv3dFunction.apply(rows, conv.weight, tuple(grid), k, s)
-    if conv.bias is not None:
-        y = y + conv.bias
-    return y, tuple((d + 2 * (k // 2) - k) // s + 1 for d in grid)
-
-
-def conv_transpose_rows(conv, rows, grid):
-    """``nn.ConvTranspose3d(2, 2, bias=False)`` on channels-last rows."""
-    from ..functions import ChannelsLastConvTranspose3dFunction
-    return ChannelsLastConvTranspose3dFunction.apply(rows, conv.weight, tuple(grid)), tuple(2 * d for d in grid)
-
-
 def bn_rows(bn, rows, grid, residual=None, relu=False):
     """A BatchNorm3d-like module on channels-last rows [V, C], optionally followed by ``+ residual`` and ``relu`` (the tails of the
     neck's blocks; on the HIP path they run inside the normalisation passes).  ``nn.BatchNorm3d`` over [1, C, X, Y, Z] is the
@@ -359,6 +352,32 @@ def bn_rows(bn, rows, grid, residual=None, relu=False):
                                                    bn.weight, bn.bias, use_batch, momentum, bn.eps))
     y = bn(rows_to_ncdhw(rows, grid, rows.shape[1]))
     return tail(y[0].permute(1, 2, 3, 0).reshape(rows.shape[0], rows.shape[1]))
+
+
+class TrainConv3d:
+    """To training what ``ConvSpec`` is to eval, with its call signature: an ``nn.Conv3d`` (k in {1, 3}, padding k // 2) or
+    ``nn.ConvTranspose3d(2, 2, bias=False)`` with a LIVE norm behind it, under autograd on channels-last rows.  Holds the two modules
+    and nothing else: the weight is read through ``train_weight_planes()`` at every call, the norm is whatever ``bn_rows`` takes."""
+
+    def __init__(self, conv, bn):
+        self.conv, self.bn, self.cout = conv, bn, conv.out_channels
+
+    def __call__(self, x, grid, residual=None, relu=0, out_mask=None, act=None):
+        """``relu`` as ``ConvSpec`` has it -- 0: bn + residual; 1: relu(bn + residual); 2: relu(bn), then + residual."""
+        from ..functions import ChannelsLastConv3dFunction, ChannelsLastConvTranspose3dFunction
+        if out_mask is not None or act is not None:
+            raise NotImplementedError("TrainConv3d: row masks and the output activation are eval-only (ConvSpec)")
+        conv, grid = self.conv, tuple(grid)
+        if isinstance(conv, torch.nn.ConvTranspose3d):
+            y, og = ChannelsLastConvTranspose3dFunction.apply(x, conv.weight, grid), tuple(2 * d for d in grid)
+        else:
+            k, s = conv.kernel_size[0], conv.stride[0]
+            y, og = ChannelsLastConv3dFunction.apply(x, conv.weight, grid, k, s), tuple((d + 2 * (k // 2) - k) // s + 1 for d in grid)
+            if conv.bias is not None:
+                y = y + conv.bias
+        if relu == 2:
+            return bn_rows(self.bn, y, og, relu=True) + residual, og
+        return bn_rows(self.bn, y, og, residual=residual, relu=bool(relu)), og
 
 
 def module_fingerprint(module):

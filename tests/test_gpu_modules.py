@@ -1204,6 +1204,66 @@ def test_neck_and_head_autograd_on_hip_kernels_matches_library_convolutions():
             assert float(torch.dot(ga, gb) / (ga.norm() * gb.norm())) > 0.9999, n
 
 
+# the neck's six layer forms: (convolution, relu, with a residual)
+TRAIN_CONV3D_FORMS = {
+    "k3s1_relu1": (lambda: torch.nn.Conv3d(32, 32, 3, 1, 1, bias=False), 1, False),
+    "k3s2_relu1": (lambda: torch.nn.Conv3d(32, 64, 3, 2, 1, bias=False), 1, False),
+    "k1s2_relu0": (lambda: torch.nn.Conv3d(32, 64, 1, 2, bias=False), 0, False),
+    "k3s1_residual_relu1": (lambda: torch.nn.Conv3d(32, 32, 3, 1, 1, bias=False), 1, True),
+    "t2_relu1": (lambda: torch.nn.ConvTranspose3d(32, 32, 2, 2, bias=False), 1, False),
+    "k3s1_residual_relu2": (lambda: torch.nn.Conv3d(32, 32, 3, 1, 1, bias=False), 2, True),
+}
+
+
+@pytest.mark.parametrize("form", sorted(TRAIN_CONV3D_FORMS))
+def test_train_conv3d_is_its_parts_bit_for_bit(form):
+    """``conv_plan.TrainConv3d(conv, bn)`` in training mode == the convolution Function, then ``bn_rows``, then ``+ residual`` for the
+    up block's form, written out here: output, running statistics and every gradient ``torch.equal``.  32 input channels on a
+    4 x 4 x 8 grid (128 rows): the smallest shapes the K tile and the even-grid rule accept, one full MFMA tile."""
+    import copy
+    from sgcdet_amd.plugin.conv_plan import TrainConv3d, bn_rows
+    from sgcdet_amd.functions import ChannelsLastConv3dFunction, ChannelsLastConvTranspose3dFunction
+    make_conv, relu, with_residual = TRAIN_CONV3D_FORMS[form]
+    torch.manual_seed(11)
+    conv = make_conv().cuda().train()
+    bn = torch.nn.BatchNorm3d(conv.out_channels).cuda().train()
+    with torch.no_grad():
+        bn.weight.uniform_(0.5, 1.5), bn.bias.normal_(0, 0.3), bn.running_mean.normal_(0, 0.3), bn.running_var.uniform_(0.5, 1.5)
+    grid = (4, 4, 8)
+    transposed = isinstance(conv, torch.nn.ConvTranspose3d)
+    k, s = conv.kernel_size[0], conv.stride[0]
+    og = tuple(2 * d for d in grid) if transposed else tuple((d + 2 * (k // 2) - k) // s + 1 for d in grid)
+    x0 = torch.randn(128, 32, device="cuda")
+    r0 = torch.randn(og[0] * og[1] * og[2], conv.out_channels, device="cuda") if with_residual else None
+    cot = torch.randn(og[0] * og[1] * og[2], conv.out_channels, device="cuda")
+
+    def run(layer):
+        c, b = copy.deepcopy(conv), copy.deepcopy(bn)
+        x = x0.clone().requires_grad_(True)
+        res = r0.clone().requires_grad_(True) if with_residual else None
+        if layer:
+            y, got_grid = TrainConv3d(c, b)(x, grid, residual=res, relu=relu)
+            assert got_grid == og
+        else:
+            if transposed:
+                y = ChannelsLastConvTranspose3dFunction.apply(x, c.weight, grid)
+            else:
+                y = ChannelsLastConv3dFunction.apply(x, c.weight, grid, k, s)
+            y = bn_rows(b, y, og, relu=True) + res if relu == 2 else bn_rows(b, y, og, residual=res, relu=bool(relu))
+        y.backward(cot)
+        out = dict(y=y.detach(), running_mean=b.running_mean, running_var=b.running_var, num_batches_tracked=b.num_batches_tracked,
+                   dx=x.grad, dw=c.weight.grad, dgamma=b.weight.grad, dbeta=b.bias.grad)
+        if with_residual:
+            out["dresidual"] = res.grad
+        return out
+
+    got, want = run(True), run(False)
+    assert got["y"].shape == (og[0] * og[1] * og[2], conv.out_channels) and float(got["y"].abs().max()) > 0
+    assert int(got["num_batches_tracked"]) == 1 and not torch.equal(got["running_mean"], bn.running_mean)
+    for name in want:
+        assert got[name] is not None and torch.equal(got[name], want[name]), name
+
+
 def test_fpn_on_hip_emits_channels_last_maps_the_path_reads_in_place():
     """Row f-1, producer side: plugin.fpn.FPN in eval mode on the GPU == its torch formulation (1e-4 of the scale), its
     outputs are channels-last in memory, and feeding them to the view transformation launches NO NCHW -> NHWC pass of the
