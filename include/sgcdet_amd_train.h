@@ -215,6 +215,27 @@ int sgc_upsample_nearest_add_backward_nhwc(const float *gout, float *gcoarse, in
 int sgc_rows_colsum(const float *x, float *out, int64_t rows, int C, float *workspace, int64_t workspace_floats, sgc_stream_t stream);
 int64_t sgc_rows_colsum_workspace_floats(int64_t rows, int C);
 
+/* ------------------------------------------------------------------------- *
+ * 14. Training DepthNet_Fusion's feature extractors: the weight gradient of the 7x7 stem (csrc/stem7_wgrad.hip)
+ * ------------------------------------------------------------------------- */
+
+/* Weight gradient of nn.Conv2d(3, 64, 7, stride = 2, padding = 3) -- the backward twin of sgc_conv2d_stem7_bf16x3 (sgcdet_amd_image.h):
+ *   dw[co][ci][kh][kw] = sum over (n, oh, ow) of dy[(n,oh,ow)][co] * img[n][ci][2 oh + kh - 3][2 ow + kw - 3]
+ *   img [N, 3, H, W] fp32 NCHW, H and W even;  dy [N * (H/2) * (W/2), 64] channels-last rows;
+ *   dw [64, 3, 7, 7]: the PARAMETER's own layout (its flattened (ci * 7 + kh) * 7 + kw is the column of the forward kernel's
+ *   [64][160] matrix), fully written; a tap outside the image adds nothing.
+ * There is no input gradient: images do not need one.
+ * bf16x3 products (always three, whatever sgc_set_conv_products says), fp32 accumulation.  The reduction rows are split over
+ * workgroups by tiles of 8 x 32 output pixels.  With a workspace of sgc_conv2d_stem7_wgrad_workspace_floats(N, H, W) floats the
+ * partial sums are added in a fixed order by a second launch (bit-identical run to run, no atomics); without one (null, or too
+ * small) one workgroup walks the whole range.  The query answers on the host: 0 for a shape that is not split (one tile), -1 for
+ * one the entry refuses (sgc_last_error() says why).
+ * SGC_EINVAL for a null or misaligned (16 bytes) pointer and for a non-positive size; SGC_EUNSUP for an odd H or W and for img or
+ * dy of 4 GiB or more. */
+int sgc_conv2d_stem7_wgrad_bf16x3(const float *img, const float *dy, float *dw, int N, int H, int W, float *workspace_or_null,
+                                  int64_t workspace_floats, sgc_stream_t stream);
+int64_t sgc_conv2d_stem7_wgrad_workspace_floats(int N, int H, int W);
+
 #ifdef __cplusplus
 }
 #endif

@@ -114,6 +114,7 @@ TRAIN_SIGNATURES = {
     "sgc_upsample_nearest_add_nhwc": [_p] * 3 + [_i] * 6 + [_p],
     "sgc_upsample_nearest_add_backward_nhwc": [_p] * 2 + [_i] * 6 + [_p],
     "sgc_rows_colsum": [_p, _p, C.c_int64, _i, _p, C.c_int64] + [_p],
+    "sgc_conv2d_stem7_wgrad_bf16x3": [_p] * 3 + [_i] * 3 + [_p, C.c_int64] + [_p],
 }
 
 TRAIN_INTROSPECTION = {
@@ -122,6 +123,7 @@ TRAIN_INTROSPECTION = {
     "sgc_head_loss_workspace_bytes": (C.c_int64, [_i] * 2),
     "sgc_conv2d_wgrad_workspace_floats": (C.c_int64, [_i] * 7),
     "sgc_rows_colsum_workspace_floats": (C.c_int64, [C.c_int64, _i]),
+    "sgc_conv2d_stem7_wgrad_workspace_floats": (C.c_int64, [_i] * 3),
 }
 
 # include/sgcdet_amd_image.h: the 2-D convolutions of the image-side CNNs (no CPU-oracle twin)

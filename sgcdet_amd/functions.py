@@ -513,6 +513,47 @@ class FrozenNormConv2dFunction(Function):
         return dx, dw, None, None, gres, None, None, None, None, db
 
 
+class Stem7ConvFunction(Function):
+    """``nn.Conv2d(3, 64, 7, stride=2, padding=3)(img) [+ bias]`` as channels-last rows, for a stem whose weight trains (the
+    ResNet-18 trunk of ``DepthNet_Fusion``; a live BatchNorm follows, so there is no epilogue beyond the bias).
+
+    ``apply(img, weight, bias)``: img [N, 3, H, W] fp32 NCHW with even H, W; weight [64, 3, 7, 7] (the module's parameter); bias
+    [64] | None -> y [N * H/2 * W/2, 64].
+
+    * forward: ``sgc_conv2d_stem7_bf16x3`` with no scale, shift = bias, no ReLU, on [64][160] planes packed from the parameter
+      here, at every call (they are 2 x 20 KB and never kept, so never stale);
+    * weight gradient: ``sgc_conv2d_stem7_wgrad_bf16x3``, which writes the parameter's own layout;
+    * bias gradient: ``sgc_rows_colsum`` of dy;
+    * images get no gradient: one that requires it is refused (its caller keeps the torch formulation)."""
+
+    @staticmethod
+    def forward(ctx, img, weight, bias=None):
+        _require_bf16_planes("Stem7ConvFunction")
+        if img.requires_grad:
+            raise RuntimeError("Stem7ConvFunction: no input gradient -- images that require grad take the torch formulation")
+        if tuple(weight.shape) != (64, 3, 7, 7) or (bias is not None and tuple(bias.shape) != (64,)):
+            raise RuntimeError("Stem7ConvFunction: needs a [64, 3, 7, 7] weight and a [64] bias (or None)")
+        ops = ext.ops()
+        w = torch.nn.functional.pad(weight.detach().float().reshape(64, 147), (0, 13)).contiguous()   # column (ci * 7 + kh) * 7 + kw
+        hi, lo = ops.split_operand(w)
+        img = img.detach().float().contiguous()
+        shift = None if bias is None else bias.detach().float().contiguous()
+        y = ops.conv2d_stem7_bf16x3(img, hi, lo, scale=None, shift=shift, relu=False)
+        ctx.save_for_backward(img)
+        ctx.dtypes = (weight.dtype, None if bias is None else bias.dtype)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        ops = ext.ops()
+        img, = ctx.saved_tensors
+        dy = dy.float().contiguous()
+        dw = ops.conv2d_stem7_wgrad_bf16x3(img, dy).to(ctx.dtypes[0]) if ctx.needs_input_grad[1] else None
+        db = ops.rows_colsum(dy).to(ctx.dtypes[1]) if ctx.dtypes[1] is not None and ctx.needs_input_grad[2] else None
+        return None, dw, db
+
+
 class UpsampleNearestAddFunction(Function):
     """The FPN's top-down step on channels-last rows: ``fine + nearest_upsample(coarse)`` to the fine map's size,
     forward ``sgc_upsample_nearest_add_nhwc`` (out of place), backward ``sgc_upsample_nearest_add_backward_nhwc`` for the coarse

@@ -6,7 +6,8 @@ it in ``__call__``.  ``conv2d_rows`` is the one rule that sends a 2-D layer to `
 ``sgc_conv2d_nhwc_ex_bf16x3`` / ``sgc_conv2d_nhwc_strided_bf16x3``: ``Conv2dSpec`` and its training twins ``FrozenConv2d`` (frozen
 norm, autograd) and ``BiasConv2d`` (no norm, trainable bias) all reach the entries through it, so the training forward is the eval forward.
 ``TrainConv3d`` is ``ConvSpec``'s training twin (convolution Function + ``bn_rows`` with a live norm and the fused tail): both are built
-by ``make(conv, bn)`` (``conv_spec`` for eval), so the neck walks one plan in either mode.  Eval BatchNorm (running statistics)
+by ``make(conv, bn)`` (``conv_spec`` for eval), so the neck walks one plan in either mode; ``TrainConv2d`` and ``TrainStem7`` are the
+same for ``Conv2dSpec`` and ``Stem7Spec`` (the depth net's feature extractors with their live norms).  Eval BatchNorm (running statistics)
 and the bias are folded into a per-channel scale / shift for the kernel's epilogue (``fold_norm``, the only copy), weights are
 permuted once to ``[tap][Cout][Cin]``, and channel counts are zero-padded to multiples of 32 (the K tile; ``_pad_to``) with zero
 weight rows, scale 1 and shift 0, so padded output columns are exactly 0.  ``cached_plan`` keeps a module's plan and rebuilds it
@@ -221,10 +222,19 @@ def conv2d_rows(x, w_hi, w_lo, nhw, k, stride=1, transposed=False, scale=None, s
                                      softmax_cols=softmax_cols)
 
 
+class Stem7Spec(Conv2dSpec):
+    """The prepared 7x7 stride-2 stem.  Called on the NCHW images: ``relu(norm(conv(img)))`` as rows, (N, H / 2, W / 2)."""
+
+    def __call__(self, img):
+        N, _, H, W = img.shape
+        y = ext.ops().conv2d_stem7_bf16x3(img.contiguous(), self.w_hi, self.w_lo, scale=self.scale, shift=self.shift, relu=True)
+        return y, (N, H // 2, W // 2)
+
+
 def stem7_spec(conv, bn):
     """The 7x7 stride-2 stem as ``sgc_conv2d_stem7_bf16x3`` reads it: [49, 64, 3] -> the [64, 160] matrix, column
     (ci * 7 + kh) * 7 + kw, 147..159 zero."""
-    stem = Conv2dSpec(conv, bn, pad_in=False)
+    stem = Stem7Spec(conv, bn, pad_in=False)
     stem.set_weight(torch.nn.functional.pad(stem.w.permute(1, 2, 0).reshape(64, 147), (0, 13)).contiguous())
     return stem
 
@@ -322,16 +332,18 @@ def train_products_ok():
     return CONV_PRODUCTS != 2
 
 
-def bn_rows(bn, rows, grid, residual=None, relu=False):
+def bn_rows(bn, rows, grid, residual=None, relu=False, image=False):
     """A BatchNorm3d-like module on channels-last rows [V, C], optionally followed by ``+ residual`` and ``relu`` (the tails of the
     neck's blocks; on the HIP path they run inside the normalisation passes).  ``nn.BatchNorm3d`` over [1, C, X, Y, Z] is the
     statistics of the V rows per channel, i.e. ``F.batch_norm`` on the [V, C] matrix (same running-statistics update); any other
-    module (SyncBatchNorm3d, GroupNorm ...) gets the 5-D channels-last view."""
+    module (SyncBatchNorm3d, GroupNorm ...) gets the 5-D channels-last view.  ``nn.BatchNorm2d`` over [N, C, H, W] is the same
+    statistics of the N * H * W rows (``grid`` = (N, H, W)) and takes the same branch; a 2-D norm of any other type
+    (``SyncBatchNorm`` ...) gets the 4-D NCHW view of the rows."""
     def tail(y):
         if residual is not None:
             y = y + residual
         return torch.relu(y) if relu else y
-    if type(bn) is torch.nn.BatchNorm3d:
+    if type(bn) in (torch.nn.BatchNorm3d, torch.nn.BatchNorm2d):
         use_batch = bn.training or (bn.running_mean is None and bn.running_var is None)
         momentum = 0.0 if bn.momentum is None else bn.momentum
         if bn.training and bn.track_running_stats and bn.num_batches_tracked is not None:
@@ -350,8 +362,68 @@ def bn_rows(bn, rows, grid, residual=None, relu=False):
         return tail(torch.nn.functional.batch_norm(rows, bn.running_mean if not bn.training or bn.track_running_stats else None,
                                                    bn.running_var if not bn.training or bn.track_running_stats else None,
                                                    bn.weight, bn.bias, use_batch, momentum, bn.eps))
+    if image:
+        y = bn(rows.view(grid[0], grid[1], grid[2], rows.shape[1]).permute(0, 3, 1, 2))
+        return tail(y.permute(0, 2, 3, 1).reshape(rows.shape[0], rows.shape[1]))
     y = bn(rows_to_ncdhw(rows, grid, rows.shape[1]))
     return tail(y[0].permute(1, 2, 3, 0).reshape(rows.shape[0], rows.shape[1]))
+
+
+class TrainConv2d:
+    """To training what ``Conv2dSpec`` is to eval, with its call signature: an ``nn.Conv2d`` (k in {1, 3}, padding k // 2, stride 1
+    or 2) with a LIVE norm behind it, under autograd on channels-last rows -- ``TrainConv3d``'s 2-D twin.  Holds the
+    two modules by reference and nothing else (``convert_sync_batchnorm`` may swap the norm between forwards): the raw convolution and
+    its trainable bias run through ``FrozenNormConv2dFunction``'s bias form (no scale, no shift, no ReLU), the norm is whatever
+    ``bn_rows`` takes.  ``bn`` None: the convolution and its bias alone (the trunk's final 1x1).  On CPU tensors the convolution is
+    torch's, on the NCHW view of the rows; the tails and the norm are the same code."""
+
+    def __init__(self, conv, bn=None):
+        self.conv, self.bn, self.cout = conv, bn, conv.out_channels
+
+    def _conv(self, x, nhw):
+        conv = self.conv
+        if x.is_cuda:
+            from ..functions import FrozenNormConv2dFunction
+            args = (x, conv.weight, None, None, None, tuple(nhw), conv.stride[0], False, False)
+            return FrozenNormConv2dFunction.apply(*args) if conv.bias is None else FrozenNormConv2dFunction.apply(*args, conv.bias)
+        y = conv(x.view(nhw[0], nhw[1], nhw[2], x.shape[1]).permute(0, 3, 1, 2))
+        return y.permute(0, 2, 3, 1).reshape(-1, self.cout)
+
+    def __call__(self, x, nhw, residual=None, relu=True, relu_after_add=False):
+        """``relu`` / ``relu_after_add`` as ``Conv2dSpec`` has them: relu(bn); relu(bn) + residual; with ``relu_after_add`` (and
+        ``relu`` False) relu(bn + residual)."""
+        s = self.conv.stride[0]
+        onhw = (nhw[0], (nhw[1] + s - 1) // s, (nhw[2] + s - 1) // s)
+        if relu and relu_after_add:
+            raise NotImplementedError("TrainConv2d: relu and relu_after_add exclude each other")
+        y = self._conv(x, nhw)
+        if self.bn is None:
+            if residual is not None or relu or relu_after_add:
+                raise NotImplementedError("TrainConv2d: a layer without a norm has no tail")
+            return y, onhw
+        if relu and residual is not None:                  # the identity block: the ReLU in the norm's pass, then the skip
+            return bn_rows(self.bn, y, onhw, relu=True, image=True) + residual, onhw
+        return bn_rows(self.bn, y, onhw, residual=residual, relu=bool(relu or relu_after_add), image=True), onhw
+
+
+class TrainStem7:
+    """``Stem7Spec``'s training twin: ``relu(bn1(conv1(img) + bias))`` with the LIVE norm.  The forward is
+    ``sgc_conv2d_stem7_bf16x3`` with the bias as its shift and no ReLU, on [64][160] planes packed from the parameter at every call
+    (``functions.Stem7ConvFunction``: its backward is ``sgc_conv2d_stem7_wgrad_bf16x3``; images get no gradient), then ``bn_rows``
+    with the ReLU.  On CPU tensors the convolution is torch's."""
+
+    def __init__(self, conv, bn):
+        self.conv, self.bn = conv, bn
+
+    def __call__(self, img):
+        N, _, H, W = img.shape
+        nhw = (N, H // 2, W // 2)
+        if img.is_cuda:
+            from ..functions import Stem7ConvFunction
+            y = Stem7ConvFunction.apply(img, self.conv.weight, self.conv.bias)
+        else:
+            y = self.conv(img).permute(0, 2, 3, 1).reshape(-1, self.conv.out_channels)
+        return bn_rows(self.bn, y, nhw, relu=True, image=True), nhw
 
 
 class TrainConv3d:

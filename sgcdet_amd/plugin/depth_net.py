@@ -19,8 +19,14 @@ The 2-D CNNs around the cost volume (``fnet_mvs``, ``fnet_mono``, the three ``Si
 kernels in eval mode on the GPU without autograd (``_forward_hip``): channels-last rows end to end,
 eval BatchNorm and biases folded into the epilogues, the ReLUs, skip additions, the channel concatenation and the softmax
 inside the convolution epilogues (``sgc_conv2d_stem7_bf16x3``, ``sgc_conv2d_nhwc_ex_bf16x3``, ``sgc_conv2d_nhwc_bf16x3``).
-The result is channels-last in memory, which is what ``SGCDet.depth_pyramid`` and the gathers read in place.  Training,
-autograd and CPU tensors keep the torch formulation (library convolutions).  ``SGC_DEPTH_NET_HIP=0`` restores
+The result is channels-last in memory, which is what ``SGCDet.depth_pyramid`` and the gathers read in place.  In train mode on
+the GPU (with or without autograd) the two feature extractors in front of the regulation U-Nets -- ``fnet_mvs`` and ``fnet_mono``,
+half of the module's arithmetic -- run on the same kernels with their BatchNorms live (``_extractors_train_hip``, DESIGN.md 4.14:
+``conv_plan.TrainConv2d`` / ``TrainStem7`` layers handed to the one walk ``fnet_mvs_rows``, the stem's weight gradient on
+``sgc_conv2d_stem7_wgrad_bf16x3``); the three ``SimpleUnet2D``s, ``depth_reg`` and the softmax keep the torch formulation there, and
+``SGC_DEPTH_NET_TRAIN_HIP=0`` restores it for the extractors (on by default: 45.1 against 51.5 ms forward + backward at config 2,
+profiles/r18_depth_net_train_bench.json).  Eval with autograd and CPU tensors keep the torch formulation (library convolutions)
+throughout.  ``SGC_DEPTH_NET_HIP=0`` restores
 it for the eval forward too (A/B runs); the kernels are the default because the whole-module A/B measured them faster
 (6.9 against 16.4 ms per 40-view scene at config 2, profiles/r10_depth_net_bench.json).  A shape the kernels do not take
 (an odd map size at a stride-2 stage, ``mono_channels`` not a multiple of 32) runs the torch formulation.
@@ -34,7 +40,8 @@ import torch.nn.functional as F
 
 from .. import ext
 from ..mmcv_lite import HEADS
-from .conv_plan import Conv2dSpec, cached_plan, image_rows, stem7_spec
+from . import conv_plan
+from .conv_plan import Conv2dSpec, TrainConv2d, TrainStem7, cached_plan, image_rows, stem7_spec
 from .plane_sweep import closest_frame_ids, plane_sweep_correlation
 
 
@@ -180,6 +187,7 @@ def homo_warping(src_fea, src_proj, ref_proj, depth_values):
 
 
 HIP_DEFAULT = "1"      # SGC_DEPTH_NET_HIP when the environment does not set it (DESIGN.md 4.10 says how it was chosen)
+TRAIN_HIP_DEFAULT = "1"      # SGC_DEPTH_NET_TRAIN_HIP likewise: the feature extractors in train mode
 
 
 # ---- the eval-mode plan of the 2-D CNNs: folded, padded, permuted layers (``Conv2dSpec``, on the device of the module) ---------
@@ -189,11 +197,37 @@ def _unet_layers(u, in_perm=None, out_perm=None):
                 conv9=Conv2dSpec(u.conv9[0], u.conv9[1]), conv11=Conv2dSpec(u.conv11[0], u.conv11[1], out_perm=out_perm))
 
 
-def _block_layers(b):
-    d = dict(conv1=Conv2dSpec(b.conv1, b.bn1), conv2=Conv2dSpec(b.conv2, b.bn2))
+def _block_layers(b, make):
+    d = dict(conv1=make(b.conv1, b.bn1), conv2=make(b.conv2, b.bn2))
     if b.downsample is not None:
-        d["down"] = Conv2dSpec(b.downsample[0], b.downsample[1])   # downsample[1] IS bn3 (registered twice): folded once, here
+        d["down"] = make(b.downsample[0], b.downsample[1])   # downsample[1] IS bn3 (registered twice): one layer, folded / normalised once
     return d
+
+
+def fnet_mvs_plan(f, make, make_stem):
+    """The layers of a ``ResNetFPN`` as ``make(conv, bn)`` / ``make_stem(conv, bn)``: ``Conv2dSpec`` and ``stem7_spec`` in eval
+    (prepared once, norms folded), ``TrainConv2d`` and ``TrainStem7`` in training (the modules, live).  ``fnet_mvs_rows`` walks it."""
+    return dict(stem=make_stem(f.conv1, f.bn1), blocks=[_block_layers(b, make) for b in list(f.layer1) + list(f.layer2)],
+                final=make(f.final_conv_3ddet, None))
+
+
+def fnet_mvs_rows(img, P):
+    """THE walk over ``fnet_mvs_plan``'s layers, eval and training: images [N, 3, H, W] -> the matching features as a logical
+    NCHW, channels-last-memory view of the final layer's rows.  A layer is called as ``Conv2dSpec`` is, the stem on the images."""
+    x, nhw = P["stem"](img)
+    for B_ in P["blocks"]:
+        y, n1 = B_["conv1"](x, nhw)
+        if "down" in B_:
+            y, _ = B_["conv2"](y, n1)                                               # relu(bn2(conv2))
+            x, _ = B_["down"](x, nhw, residual=y, relu=False, relu_after_add=True)  # relu(bn3(conv1x1(x)) + y)
+        else:
+            # relu(.) + x with x >= 0: the outer ReLU is a no-op, for the gradient too -- where the sum is 0 both addends are 0 and
+            # came through closed ReLU gates, so either formulation sends 0 down both paths
+            x, _ = B_["conv2"](y, n1, residual=x)
+        nhw = n1
+    f, _ = P["final"](x, nhw, relu=False)
+    C = P["final"].cout
+    return f.view(nhw[0], nhw[1], nhw[2], f.shape[1])[..., :C].permute(0, 3, 1, 2)      # logical NCHW, channels-last memory
 
 
 def depth_net_plan(net):
@@ -203,7 +237,7 @@ def depth_net_plan(net):
     ``fusion_regulation.conv11`` (whose skip is that buffer) are permuted to that order here.  ``cat_perm[new] = module index``."""
     D, f = net.depth_channels, net.fnet_mvs
     cat_perm = torch.cat([torch.arange(D, D + 128), torch.arange(D)]).to(net.depth_reg.weight.device)
-    return dict(stem=stem7_spec(f.conv1, f.bn1), blocks=[_block_layers(b) for b in list(f.layer1) + list(f.layer2)], final=Conv2dSpec(f.final_conv_3ddet),
+    return dict(**fnet_mvs_plan(f, Conv2dSpec, stem7_spec),
                 corr=_unet_layers(net.correlation_regulation), fnet_mono=Conv2dSpec(net.fnet_mono.conv, net.fnet_mono.bn),
                 mono=_unet_layers(net.mono_regulation), fusion=_unet_layers(net.fusion_regulation, in_perm=cat_perm, out_perm=cat_perm),
                 depth_reg=Conv2dSpec(net.depth_reg, in_perm=cat_perm, pad_out=False), cat_perm=cat_perm)
@@ -274,22 +308,7 @@ class DepthNet_Fusion(nn.Module):
         return y
 
     def _fnet_mvs_hip(self, img, P):
-        ops = ext.ops()
-        N, _, Hi, Wi = img.shape
-        st = P["stem"]
-        x = ops.conv2d_stem7_bf16x3(img.contiguous(), st.w_hi, st.w_lo, scale=st.scale, shift=st.shift, relu=True)
-        nhw = (N, Hi // 2, Wi // 2)
-        for B_ in P["blocks"]:
-            y, n1 = B_["conv1"](x, nhw)
-            if "down" in B_:
-                y, _ = B_["conv2"](y, n1)                                               # relu(bn2(conv2))
-                x, _ = B_["down"](x, nhw, residual=y, relu=False, relu_after_add=True)  # relu(bn3(conv1x1(x)) + y)
-            else:
-                x, _ = B_["conv2"](y, n1, residual=x)                                   # relu(.) + x, x >= 0: the outer ReLU is a no-op
-            nhw = n1
-        f, _ = P["final"](x, nhw, relu=False)
-        C = P["final"].cout
-        return f.view(nhw[0], nhw[1], nhw[2], f.shape[1])[..., :C].permute(0, 3, 1, 2)      # logical NCHW, channels-last memory
+        return fnet_mvs_rows(img, P)
 
     def _forward_hip(self, xs, imgs, img_metas, stride):
         ops = ext.ops()
@@ -310,19 +329,49 @@ class DepthNet_Fusion(nn.Module):
             P["depth_reg"](fused, nhw, relu=False, out=out[b].view(N * H * W, D), softmax_cols=D)
         return out.permute(0, 1, 4, 2, 3)                     # [B, N, D, H, W]; every [N, D, H, W] slice channels-last in memory
 
+    # ---- train mode on the GPU: the two feature extractors on the kernels, live BatchNorm ----------
+    def _train_hip_ok(self, xs, imgs):
+        """Does the train-mode forward run ``fnet_mvs`` and ``fnet_mono`` on the kernels?  Train mode with or without autograd (a
+        ``no_grad`` call in train mode computes the numbers of the training step), fp32 GPU tensors of the shapes ``_forward_hip``
+        takes, images that need no gradient (the stem has no input gradient), an arithmetic mode the training Functions accept,
+        and no ``SGC_DEPTH_NET_TRAIN_HIP=0``."""
+        return (self.training and xs.is_cuda and imgs.is_cuda and not imgs.requires_grad
+                and os.environ.get("SGC_DEPTH_NET_TRAIN_HIP", TRAIN_HIP_DEFAULT) != "0"
+                and conv_plan.CONV_MODE == "bf16x3" and conv_plan.train_products_ok() and self._hip_ok(xs, imgs))
+
+    def _extractors_train_hip(self, x, img):
+        """(f_mvs, fnet_mono(x)) of one scene as logical-NCHW, channels-last-memory views of the kernels' rows.  The layers are built
+        per forward and only point at the modules: nothing outlives a ``convert_sync_batchnorm`` that replaces the norms."""
+        from ..functions import NchwToRowsFunction
+        f_mvs = fnet_mvs_rows(img, fnet_mvs_plan(self.fnet_mvs, TrainConv2d, TrainStem7))
+        N, C, H, W = x.shape
+        if x.is_contiguous(memory_format=torch.channels_last) and x.dtype == torch.float32:
+            rows = x.permute(0, 2, 3, 1).reshape(N * H * W, C)
+        else:
+            rows = NchwToRowsFunction.apply(x).view(N * H * W, C)
+        m, _ = TrainConv2d(self.fnet_mono.conv, self.fnet_mono.bn)(rows, (N, H, W))
+        return f_mvs, m.view(N, H, W, m.shape[1]).permute(0, 3, 1, 2)
+
     def forward(self, xs, imgs, img_metas, stride):
         """xs [B,N,C,H,W] (finest FPN map), imgs [B,N,3,4H,4W], img_metas list of B dicts -> depth probability
         [B,N,D,H,W] (softmax over the D bins).  Eval mode on the GPU without autograd: ``_forward_hip`` (the result is
-        channels-last in memory); otherwise the torch formulation below."""
+        channels-last in memory).  Train mode on the GPU: the feature extractors on the kernels (``_extractors_train_hip``), the
+        U-Nets, ``depth_reg`` and the softmax in the torch formulation below; everything else is that formulation throughout."""
         if (not self.training and not torch.is_grad_enabled() and xs.is_cuda and imgs.is_cuda
                 and os.environ.get("SGC_DEPTH_NET_HIP", HIP_DEFAULT) != "0" and self._hip_ok(xs, imgs)):
             return self._forward_hip(xs, imgs, img_metas, stride)
+        train_hip = self._train_hip_ok(xs, imgs)
         B, num_src, C, H, W = xs.shape
         depth_preds = torch.empty((B, num_src, self.depth_channels, H, W), device=xs.device)
         for b, (x, img, img_meta) in enumerate(zip(xs, imgs, img_metas)):
-            f_mvs = self.fnet_mvs(img)
-            cost_reg = self.correlation_regulation(self.correlation(f_mvs, img_meta, stride))
-            mono_reg = self.mono_regulation(self.fnet_mono(x))
+            if train_hip:
+                f_mvs, mono = self._extractors_train_hip(x, img)
+                cost_reg = self.correlation_regulation(self.correlation(f_mvs, img_meta, stride))
+                mono_reg = self.mono_regulation(mono)
+            else:
+                f_mvs = self.fnet_mvs(img)
+                cost_reg = self.correlation_regulation(self.correlation(f_mvs, img_meta, stride))
+                mono_reg = self.mono_regulation(self.fnet_mono(x))
             prob = self.depth_reg(self.fusion_regulation(torch.cat([cost_reg, mono_reg], dim=1)))
             depth_preds[b] = F.softmax(prob, dim=1)
         return depth_preds

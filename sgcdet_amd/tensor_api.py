@@ -1181,6 +1181,31 @@ class TensorOps:
                    _meta=dict(V=dy.shape[0], Cin=Cin, Cout=Cout, taps=ksize * ksize, OV=dy.shape[0]))
         return dw
 
+    def conv2d_stem7_wgrad_workspace_floats(self, N, H, W):
+        """Floats of the workspace ``conv2d_stem7_wgrad_bf16x3`` sums its split reduction through; 0: the shape is not split."""
+        n = int(self.lib._dll.sgc_conv2d_stem7_wgrad_workspace_floats(N, H, W))
+        if n < 0:
+            raise RuntimeError("conv2d_stem7_wgrad_bf16x3: " + self.lib.last_error())
+        return n
+
+    def conv2d_stem7_wgrad_bf16x3(self, img, dy, workspace=True):
+        """dW [64, 3, 7, 7] (the parameter's layout) of the 7x7 stride-2 padding-3 stem: img [N, 3, H, W] NCHW, dy
+        [N*(H/2)*(W/2), 64] rows (``sgc_conv2d_stem7_wgrad_bf16x3``, include/sgcdet_amd_train.h).  ``workspace=False``: no
+        workspace is passed, one workgroup walks the whole reduction."""
+        self._check(img=img, dy=dy)
+        self._f32(img=img, dy=dy)
+        if img.dim() != 4 or img.shape[1] != 3 or img.shape[2] % 2 or img.shape[3] % 2:
+            raise RuntimeError("conv2d_stem7_wgrad_bf16x3: img must be [N, 3, H, W] with even H and W")
+        N, _, H, W = img.shape
+        if dy.dim() != 2 or dy.shape != (N * (H // 2) * (W // 2), 64):
+            raise RuntimeError("conv2d_stem7_wgrad_bf16x3: dy must be [N * H/2 * W/2, 64]")
+        n = self.conv2d_stem7_wgrad_workspace_floats(N, H, W) if workspace else 0
+        ws = torch.empty(n, dtype=torch.float32, device=img.device) if n > 0 else None
+        dw = torch.empty((64, 3, 7, 7), dtype=torch.float32, device=img.device)
+        self._call("sgc_conv2d_stem7_wgrad_bf16x3", img, dy, dw, N, H, W, ws, n,
+                   _meta=dict(V=dy.shape[0], Cin=3, Cout=64, taps=49, OV=dy.shape[0]))
+        return dw
+
     def frozen_norm_act_backward(self, dy, y=None, scale=None, relu=False, want_gres=False):
         """Backward of a frozen-norm epilogue (``sgc_frozen_norm_act_backward``): dy, y [rows, C] -> (g, gres | None) with
         g = gate * dy * scale, gres = gate * dy, gate = (y > 0) with ``relu`` else 1."""
