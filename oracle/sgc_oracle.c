@@ -1253,9 +1253,9 @@ int sgc_conv3d_winograd_z_bf16x3(const float *x, const uint16_t *wg_hi, const ui
             const double a = q == 0 ? m[co] + m[Cout + co] + m[2 * Cout + co] : m[Cout + co] - m[2 * Cout + co] - m[3 * Cout + co];
             const int64_t o = (((int64_t)xx * iy + yy) * iz + 2 * j + q) * Cout + co;
             float v = (float)a * (scale ? scale[co] : 1.f) + (shift ? shift[co] : 0.f);
-            if (relu == 2) v = v > 0.f ? v : 0.f;
+            if (relu == 2 && v < 0.f) v = 0.f;                    /* a NaN stays a NaN, as in torch.relu */
             if (residual_or_null) v += residual_or_null[o];
-            if (relu == 1) v = v > 0.f ? v : 0.f;
+            if (relu == 1 && v < 0.f) v = 0.f;
             y[o] = v;
           }
       }
@@ -1504,7 +1504,7 @@ int sgc_bn_rows_act_forward(const float *x, const float *weight, const float *bi
   for (int64_t i = 0; i < (int64_t)rows * C; ++i) {
     float v = y[i];
     if (residual_or_null) v += residual_or_null[i];
-    if (relu) v = v > 0.f ? v : 0.f;
+    if (relu && v < 0.f) v = 0.f;                                 /* a NaN stays a NaN, as in torch.relu */
     y[i] = v;
   }
   return SGC_OK;
@@ -1515,7 +1515,7 @@ int sgc_bn_rows_act_backward(const float *x, const float *dy, const float *y_rel
   if (!dy) return fail(SGC_EINVAL, "sgc_bn_rows_act_backward: null pointer");
   const int64_t n = (int64_t)rows * C;
   float *g = (float *)malloc(sizeof(float) * (size_t)(n > 0 ? n : 1));
-  for (int64_t i = 0; i < n; ++i) g[i] = (!y_relu_or_null || y_relu_or_null[i] > 0.f) ? dy[i] : 0.f;
+  for (int64_t i = 0; i < n; ++i) g[i] = (y_relu_or_null && y_relu_or_null[i] <= 0.f) ? 0.f : dy[i];   /* a NaN y passes dy: threshold_backward */
   if (dresidual_or_null) memcpy(dresidual_or_null, g, sizeof(float) * (size_t)n);
   const int rc = sgc_bn_rows_backward(x, g, mean, invstd, weight, dx, dweight, dbias, workspace, workspace_floats, rows, C, stream);
   free(g);

@@ -120,7 +120,7 @@ __global__ __launch_bounds__(BN_T) void bn_apply_kernel(const float4 *__restrict
     o.x = (v.x - m.x) * s.x * ww.x + bb.x; o.y = (v.y - m.y) * s.y * ww.y + bb.y;
     o.z = (v.z - m.z) * s.z * ww.z + bb.z; o.w = (v.w - m.w) * s.w * ww.w + bb.w;
     if (residual) { const float4 r = residual[i]; o.x += r.x; o.y += r.y; o.z += r.z; o.w += r.w; }
-    if (relu) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
+    if (relu) o = relu_nan(o);
     y[i] = o;
   }
 }
@@ -146,7 +146,7 @@ __global__ __launch_bounds__(BN_T) void bn_bwd_partial_kernel(const float *__res
         float4 g4 = *reinterpret_cast<const float4 *>(dy + (int64_t)r * C + c4 * 4);
         if (y_or_null) {
           const float4 y4 = *reinterpret_cast<const float4 *>(y_or_null + (int64_t)r * C + c4 * 4);
-          g4.x = y4.x > 0.f ? g4.x : 0.f; g4.y = y4.y > 0.f ? g4.y : 0.f; g4.z = y4.z > 0.f ? g4.z : 0.f; g4.w = y4.w > 0.f ? g4.w : 0.f;
+          g4.x = y4.x <= 0.f ? 0.f : g4.x; g4.y = y4.y <= 0.f ? 0.f : g4.y; g4.z = y4.z <= 0.f ? 0.f : g4.z; g4.w = y4.w <= 0.f ? 0.f : g4.w;   // a NaN y passes, as in torch
         }
         const float v[4] = {v4.x, v4.y, v4.z, v4.w}, g[4] = {g4.x, g4.y, g4.z, g4.w};
 #pragma unroll
@@ -209,7 +209,7 @@ __global__ __launch_bounds__(BN_T) void bn_bwd_apply_kernel(const float4 *__rest
     float4 g4 = dy[i];
     if (y_or_null) {
       const float4 y4 = y_or_null[i];
-      g4.x = y4.x > 0.f ? g4.x : 0.f; g4.y = y4.y > 0.f ? g4.y : 0.f; g4.z = y4.z > 0.f ? g4.z : 0.f; g4.w = y4.w > 0.f ? g4.w : 0.f;
+      g4.x = y4.x <= 0.f ? 0.f : g4.x; g4.y = y4.y <= 0.f ? 0.f : g4.y; g4.z = y4.z <= 0.f ? 0.f : g4.z; g4.w = y4.w <= 0.f ? 0.f : g4.w;   // a NaN y passes, as in torch
     }
     if (dres_or_null) dres_or_null[i] = g4;        // the gradient of the added identity: the masked incoming gradient
     const float v[4] = {v4.x, v4.y, v4.z, v4.w}, g[4] = {g4.x, g4.y, g4.z, g4.w};

@@ -24,6 +24,12 @@ inline int check_launch(const char *what) {
 
 inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
+// The ReLU of every epilogue.  torch.relu(NaN) is NaN and the oracle keeps it too (`v < 0 ? 0 : v`); fmaxf(NaN, 0) is 0, which
+// turns a poisoned activation into a clean zero that no loss ever sees (DESIGN.md "Non-finite values").  Finite values are those
+// of fmaxf up to the sign of a zero.  Running maxima, IoU terms and depth clamps keep fmaxf.
+__device__ __forceinline__ float relu_nan(float v) { return v < 0.f ? 0.f : v; }
+__device__ __forceinline__ float4 relu_nan(float4 v) { return make_float4(relu_nan(v.x), relu_nan(v.y), relu_nan(v.z), relu_nan(v.w)); }
+
 // hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE attribute: `done` is a bitmask over device ordinals
 // (one static per call site), so a process that drives several GPUs sets it once on each of them; thread-safe
 // (setting it twice is harmless, the mask only saves the driver call on the hot path).

@@ -278,7 +278,7 @@ __global__ __launch_bounds__(256) void conv2d_stem7_kernel(const StemParams p) {
           const int ow = ow0 + (k & 3) + 8 * (k >> 2) + 4 * (lane >> 5);
           if (ow >= p.OW) continue;
           float v = acc[i][j][k] * sc + sh;
-          if (p.relu) v = fmaxf(v, 0.f);
+          if (p.relu) v = relu_nan(v);
           p.y[(((int64_t)n * p.OH + oh) * p.OW + ow) * 64 + col] = v;
         }
       }

@@ -113,12 +113,12 @@ __global__ void conv_epilogue_kernel(float *__restrict__ y, const float *__restr
     const float4 sc = scale ? reinterpret_cast<const float4 *>(scale)[c] : make_float4(1.f, 1.f, 1.f, 1.f);
     const float4 sh = shift ? reinterpret_cast<const float4 *>(shift)[c] : make_float4(0.f, 0.f, 0.f, 0.f);
     v.x = v.x * sc.x + sh.x; v.y = v.y * sc.y + sh.y; v.z = v.z * sc.z + sh.z; v.w = v.w * sc.w + sh.w;
-    if (relu == 2) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+    if (relu == 2) v = relu_nan(v);
     if (residual) {
       const float4 r = reinterpret_cast<const float4 *>(residual)[i];
       v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
     }
-    if (relu == 1) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+    if (relu == 1) v = relu_nan(v);
     if (act_scale) v = act_col4(v, c * 4, act_c0, act_c1, *act_scale);
     reinterpret_cast<float4 *>(y)[i] = v;
   }
@@ -170,12 +170,12 @@ __global__ __launch_bounds__(256) void winograd_z_out_kernel(const float4 *__res
     for (int q = 0; q < 2; ++q) {
       float4 w = v[q];
       w.x = w.x * sc.x + sh.x; w.y = w.y * sc.y + sh.y; w.z = w.z * sc.z + sh.z; w.w = w.w * sc.w + sh.w;
-      if (relu == 2) { w.x = fmaxf(w.x, 0.f); w.y = fmaxf(w.y, 0.f); w.z = fmaxf(w.z, 0.f); w.w = fmaxf(w.w, 0.f); }
+      if (relu == 2) w = relu_nan(w);
       if (residual) {
         const float4 rr = residual[o0 + (int64_t)q * C4];
         w.x += rr.x; w.y += rr.y; w.z += rr.z; w.w += rr.w;
       }
-      if (relu == 1) { w.x = fmaxf(w.x, 0.f); w.y = fmaxf(w.y, 0.f); w.z = fmaxf(w.z, 0.f); w.w = fmaxf(w.w, 0.f); }
+      if (relu == 1) w = relu_nan(w);
       if (act_scale) w = act_col4(w, c * 4, act_c0, act_c1, *act_scale);
       y[o0 + (int64_t)q * C4] = w;
     }

@@ -161,9 +161,9 @@ __global__ __launch_bounds__(512) void conv3d_halo_bf16x3_kernel(const ConvParam
           float v = 0.f;
           if (p.splitk > 1) { p.ws[(int64_t)blockIdx.z * p.ws_stride + orow * p.Cout + col + q] = 0.f; continue; }
           v = v * (p.scale ? p.scale[col + q] : 1.f) + (p.shift ? p.shift[col + q] : 0.f);
-          if (p.relu == 2) v = fmaxf(v, 0.f);
+          if (p.relu == 2) v = relu_nan(v);
           if (p.residual) v += p.residual[orow * p.Cout + col + q];
-          if (p.relu == 1) v = fmaxf(v, 0.f);
+          if (p.relu == 1) v = relu_nan(v);
           if (p.act_scale) v = act_col(v, col + q, p.act_c0, p.act_c1, *p.act_scale);
           p.y[orow * p.Cout + col + q] = v;
         }
@@ -459,12 +459,12 @@ __global__ __launch_bounds__(512) void conv3d_halo_bf16x3_kernel(const ConvParam
         const float4 sh4 = *reinterpret_cast<const float4 *>(p.shift + col);
         v.x += sh4.x; v.y += sh4.y; v.z += sh4.z; v.w += sh4.w;
       }
-      if (p.relu == 2) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+      if (p.relu == 2) v = relu_nan(v);
       if (p.residual) {
         const float4 r4 = *reinterpret_cast<const float4 *>(p.residual + orow * p.Cout + col);
         v.x += r4.x; v.y += r4.y; v.z += r4.z; v.w += r4.w;
       }
-      if (p.relu == 1) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+      if (p.relu == 1) v = relu_nan(v);
       if (p.act_scale) v = act_col4(v, col, p.act_c0, p.act_c1, *p.act_scale);
       *reinterpret_cast<float4 *>(p.y + orow * p.Cout + col) = v;
     }
@@ -490,9 +490,9 @@ __global__ __launch_bounds__(512) void conv3d_halo_bf16x3_kernel(const ConvParam
           else atomicAdd(dst, acc[i][j][k]);
         } else {
           float v = acc[i][j][k] * sc + sh;
-          if (p.relu == 2) v = fmaxf(v, 0.f);
+          if (p.relu == 2) v = relu_nan(v);
           if (p.residual) v += p.residual[orow * p.Cout + col];
-          if (p.relu == 1) v = fmaxf(v, 0.f);
+          if (p.relu == 1) v = relu_nan(v);
           if (p.act_scale) v = act_col(v, col, p.act_c0, p.act_c1, *p.act_scale);
           *dst = v;
         }

@@ -161,9 +161,9 @@ __global__ __launch_bounds__(256) void conv3d_igemm_f32_kernel(const ConvParams 
           else atomicAdd(dst, acc[i][j][k]);
         } else {
           float v = acc[i][j][k] * sc + sh;
-          if (p.relu == 2) v = fmaxf(v, 0.f);
+          if (p.relu == 2) v = relu_nan(v);
           if (p.residual) v += p.residual[orow * p.Cout + col];
-          if (p.relu == 1) v = fmaxf(v, 0.f);
+          if (p.relu == 1) v = relu_nan(v);
           if (p.act_scale) v = act_col(v, col, p.act_c0, p.act_c1, *p.act_scale);
           *dst = v;
         }
@@ -344,9 +344,9 @@ __global__ __launch_bounds__(WM * WN * 64) void conv3d_igemm_bf16x3_kernel(const
           else atomicAdd(dst, t.acc[i][j][k]);
         } else {
           float v = t.acc[i][j][k] * sc + sh;
-          if (p.relu == 2) v = fmaxf(v, 0.f);
+          if (p.relu == 2) v = relu_nan(v);
           if (p.residual) v += p.residual[orow * p.Cout + col];
-          if (p.relu == 1) v = fmaxf(v, 0.f);
+          if (p.relu == 1) v = relu_nan(v);
           if (p.act_scale) v = act_col(v, col, p.act_c0, p.act_c1, *p.act_scale);
           *dst = v;
         }

@@ -21,7 +21,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t tile_rsrc(const void *ptr, int
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(ptr), 0, (int)(unsigned)bytes, 0x00020000);
 }
 
-__device__ __forceinline__ float4 relu4(float4 v) { return make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)); }
+__device__ __forceinline__ float4 relu4(float4 v) { return relu_nan(v); }
 
 // v * scale[col ..] + shift[col ..]; relu; + residual[roff ..]; relu -- every vector optional, 16 bytes at a time
 __device__ __forceinline__ float4 epilogue4(float4 v, int col, const float *scale, const float *shift, bool relu_before,

@@ -174,7 +174,7 @@ __global__ __launch_bounds__(C * 2, 2) void level_tail_kernel(const LevelTailPar
       __bf16 *hh = H_hi + 4 * fh * PH + hc, *hl = H_lo + 4 * fh * PH + hc;
 #pragma unroll
       for (int k = 0; k < 16; ++k) {
-        const float v = fmaxf(acc[k] + sh, 0.f);
+        const float v = relu_nan(acc[k] + sh);
         const __bf16 hb = op_hi<NP>(v);
         hh[acc_row(k) * PH] = hb;
         hl[acc_row(k) * PH] = op_lo<NP>(v, hb);

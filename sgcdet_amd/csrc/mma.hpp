@@ -30,7 +30,8 @@ __device__ __forceinline__ __bf16 op_hi(float v) {
     return (__bf16)v;
   }
 }
-// the low part of the NP = 3 split; unused (zero bits) in the one-product modes
+// the low part of the NP = 3 split; unused (zero bits) in the one-product modes.  An infinite v gives hi = v and lo = Inf - Inf = NaN:
+// every MFMA kernel turns an Inf operand into NaN (bounded by the traced contract of DESIGN.md "Non-finite values"); a NaN stays NaN
 template <int NP>
 __device__ __forceinline__ __bf16 op_lo(float v, __bf16 hi) {
   if constexpr (NP == 3) return (__bf16)(v - (float)hi);

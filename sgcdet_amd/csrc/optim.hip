@@ -149,7 +149,7 @@ __global__ __launch_bounds__(kOptThreads) void adamw_step_batch_kernel(const Opt
   k.clip = 1.f;
   if (norm != nullptr && max_norm > 0.f) {           // clip_grad_norm_: clamp(max_norm / (total_norm + 1e-6), max = 1)
     const float c = max_norm / (norm[0] + 1e-6f);
-    k.clip = c < 1.f ? c : 1.f;
+    k.clip = c > 1.f ? 1.f : c;                     // a NaN norm stays NaN, as torch.clamp(max = 1) keeps it: every gradient is poisoned
   }
   k.decay = (float)(1.0 - gr.lr * gr.weight_decay);
   k.w1 = (float)(1.0 - gr.beta1);

@@ -147,10 +147,10 @@ __device__ __forceinline__ void rows_store_rowmajor(const f32x16 &acc, __amdgpu_
     float v = acc[k] * sc;                              // two roundings (product, then sum) like the staged epilogue of
     asm volatile("" : "+v"(v));                          // the tile kernel and the oracle's plain C: the empty asm keeps the
     v += sh;                                             // compiler from contracting them into one fma
-    v = relu_before ? fmaxf(v, 0.f) : v;
+    v = relu_before ? relu_nan(v) : v;
     if constexpr (RESIDUAL) {
       v += res[k];
-      v = relu_after ? fmaxf(v, 0.f) : v;
+      v = relu_after ? relu_nan(v) : v;
     }
     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), yr, base + acc_row(k) * n4, 0, 0);
   }

@@ -97,7 +97,8 @@ __global__ __launch_bounds__(256, 2) void conv2d_stem7_wgrad_kernel(const Stem7W
         bf16x8 bh, bl;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          const float v = koff[j] >= 0 ? patch[rbase + koff[j] + 2 * e] : 0.f;
+          // a pixel outside the map takes no patch element either: its dy is 0, but 0 * NaN would poison a tap that never reads that pixel
+          const float v = koff[j] >= 0 && ow + e < p.OW ? patch[rbase + koff[j] + 2 * e] : 0.f;
           const __bf16 hb = op_hi<3>(v);
           bh[e] = hb;
           bl[e] = op_lo<3>(v, hb);

@@ -827,8 +827,8 @@ extern "C" int sgc_upsample2x_occ(const float *vol, const float *w_or_null, cons
   return check_launch("upsample2x_occ_kernel");
 }
 
-// Adjoint of the x2 trilinear upsample on NCDHW planes as a gather: one thread per input voxel collects its <= 4 x 4 x 4
-// outputs (per axis: 2i-1, 2i, 2i+1, 2i+2) with the weights the forward's index rule gives them.  torch's backward
+// Adjoint of the x2 trilinear upsample on NCDHW planes as a gather: one thread per input voxel collects its <= 5 x 5 x 5
+// outputs (per axis: 2i-1, 2i, 2i+1, 2i+2, and output 0 for i = 1) with the weights the forward's index rule gives them.  torch's backward
 // scatters 8 float atomics per output element (5.2 ms per config-2 training step for the two upsamples of the path).
 __device__ __forceinline__ float up2_weight(int o, int n, int i) {     // weight of input i in output o along one axis
   float t = 0.5f * ((float)o + 0.5f) - 0.5f;
@@ -849,12 +849,14 @@ __global__ __launch_bounds__(256) void upsample2x_backward_kernel(const float *_
     const int z = (int)(v % Z), y = (int)((v / Z) % Y), x = (int)(v / ((int64_t)Z * Y));
     const float *plane = go + (int64_t)c * vin * 8;
     float acc = 0.f;
-    for (int ox = max(2 * x - 1, 0); ox <= min(2 * x + 2, 2 * X - 1); ++ox) {
+    // input 1 also takes output 0, with weight exactly 0 (the forward clamps t to 0 there: i0 = 0, i1 = 1, l1 = 0): torch's scatter
+    // adds that 0 * go, which is NaN for a non-finite go, and so does this gather
+    for (int ox = x == 1 ? 0 : max(2 * x - 1, 0); ox <= min(2 * x + 2, 2 * X - 1); ++ox) {
       const float wx = up2_weight(ox, X, x);
-      for (int oy = max(2 * y - 1, 0); oy <= min(2 * y + 2, OY - 1); ++oy) {
+      for (int oy = y == 1 ? 0 : max(2 * y - 1, 0); oy <= min(2 * y + 2, OY - 1); ++oy) {
         const float wxy = wx * up2_weight(oy, Y, y);
         const float *line = plane + ((int64_t)ox * OY + oy) * OZ;
-        for (int oz = max(2 * z - 1, 0); oz <= min(2 * z + 2, OZ - 1); ++oz) acc += wxy * up2_weight(oz, Z, z) * line[oz];
+        for (int oz = z == 1 ? 0 : max(2 * z - 1, 0); oz <= min(2 * z + 2, OZ - 1); ++oz) acc += wxy * up2_weight(oz, Z, z) * line[oz];
       }
     }
     gi[e] = acc;
