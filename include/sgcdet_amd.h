@@ -190,8 +190,10 @@ int sgc_dfa3d_backward_items(const float *value, const float *dist, const int64_
  * value [N,S,M,Cm], dist [N,S,D] (one depth map per camera: dist_heads == 1), loc3 [n_items, loc_heads, P, 3], attn
  * [n_items, loc_heads, P] or NULL (= 1), grad_out [n_items, M*Cm]; loc_heads = M, or 1 = ONE sample set shared by the M channel
  * groups (the geometry sample's single head over C = M * Cm channels); its gradients are then summed over the groups.
- * grad_value / grad_dist must be zero-filled by the caller (they are accumulated into); grad_loc3 / grad_attn (either may be NULL)
- * are written.  Cm in {16, 32}, P <= 4; the window (bin + halo) must fit LDS (sgc_dfa3d_backward_binned_lds_bytes <= 160 KiB).
+ * grad_value / grad_dist must be zero-filled by the caller (they are accumulated into).  grad_loc3 / grad_attn (either may be NULL):
+ * with loc_heads == M every element is written once; with loc_heads == 1 < M the M channel-group workgroups of a (camera, bin) ADD
+ * their parts with atomics, so the caller must zero-fill them too (the Python wrapper does).
+ * Cm in {16, 32}, P <= 4; the window (bin + halo) must fit LDS (sgc_dfa3d_backward_binned_lds_bytes <= 160 KiB).
  * head_shift_or_null [M][2] int32 (x, y) in pixels: head m's window is shifted by it (its mean sampling offset; speed only).
  * Same function of the inputs as sgc_dfa3d_backward_items; float atomics make the last bits order-dependent in both. */
 int sgc_dfa3d_backward_binned(const float *value, const float *dist, const float *loc3, const float *attn_or_null,
@@ -347,6 +349,20 @@ int sgc_depth_pairs(const float *dist, float *dp, int N, int H, int W, int D, in
 /* ------------------------------------------------------------------------- *
  * 5. Inter-view aggregation (TU/deformable_cross_attention.py:815-837)
  * ------------------------------------------------------------------------- */
+
+/* Capacity tails: what the kernels leave UNWRITTEN (the memory keeps whatever it held; no consumer in this library reads it).
+ *   sgc_compact_pairs               pair_cam / pair_q beyond totals[0] (n_pairs), valid_index beyond totals[1] (n_valid)
+ *   sgc_bin_pairs                   pair_q_out / pair_ref beyond the pair count (cam_offset[N])
+ *   sgc_pairs_geometry_sample, sgc_pairs_geometry_linear_bf16x3, sgc_pairs_deform_gather, sgc_pairs_deform_gather_tiled
+ *                                   rows of out / y beyond the pair count (host count, totals[0], or bin_offset's last entry)
+ *   sgc_view_mean, sgc_view_attend, sgc_view_attend_pq, sgc_linear_rows_*_bf16x3, sgc_layer_norm_rows, sgc_scatter_rows
+ *                                   rows beyond min(host count, *device count)
+ *   sgc_aligned_nms3d               keep beyond n_keep[0];   sgc_nms_rotated_bev: keep[c] beyond n_keep[c]
+ *   sgc_conv3d_cl_bf16x3_masked / _act with a mask: rows with mask 0 are written, with the epilogue of a zero accumulator or the
+ *                                   dense value (finite for finite inputs), see there
+ * Everything else an entry point names as OUT is written in full by every launch, whatever it held before, and no launch writes
+ * outside the extents given here; a workspace needs nothing from its previous contents (tests/buffer_contract.py holds every entry
+ * point to this). */
 
 /* Row counts that live on the device.  sgc_compact_pairs leaves {n_pairs, n_valid, ...} in totals[]; the entry
  * points below take an optional `*_dev_or_null` pointer to such a count next to the host-side integer: when it
