@@ -61,7 +61,10 @@ int sgc_abi_version(void);
  * "split_max": the tile kernel splits at any K step, see pick_split_steps in csrc/conv3d.hip) choose over how many workgroups a
  * layer with few voxels splits its reduction -- a different split adds the same partial sums in another order (fp32 rounding,
  * <= 1e-5 of the tensor scale; deterministic for a given value).  sgc_conv3d_workspace_floats follows the current values:
- * query it under the setting the call will run with.                                                                       */
+ * query it under the setting the call will run with.  The second exception: "wz_mfma" (16 default | 32) selects the matrix
+ * instruction of the Winograd-z bricks of sgc_conv3d_winograd_z_bf16x3, v_mfma_f32_16x16x32 or v_mfma_f32_32x32x16 -- the
+ * instruction sums its products in another order (fp32 rounding: measured 2e-7 .. 9e-7 of the tensor scale between the two
+ * values, tested <= 1e-5; deterministic for a given value, the same on both bricks).                                        */
 int sgc_set_tuning(const char *key, int value);
 /* Arithmetic mode of every bf16 MFMA kernel of the library (sgc_conv3d_cl_bf16x3 and its 2-D / masked forms,
  * sgc_linear_rows_*_bf16x3, sgc_level_tail):

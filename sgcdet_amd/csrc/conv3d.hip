@@ -19,6 +19,11 @@ int g_conv_products = 3;     // NOT a tuning knob (it changes results; sgc_set_c
 //   wz_brick      Winograd-z stack, alternated with four scenes in flight (bit-identical results): 2 images x 10 x 10 on the three
 //                 20x20x8 layers 526.8 against 515.8 scenes/s for 4 x 8 x 8, +7 .. +11 in three jobs (profiles/r15_wz_bricks.md)
 //                 -> the brick with fewer matrix rows, 4 x 8 x 8 on a tie
+//   wz_mfma       Winograd-z bricks on v_mfma_f32_16x16x32 (16) or 32x32x16 (32): the chip holds a higher clock on the 16x16x32 shape
+//                 under load (bare loops on random data, 2 waves per SIMD: 2 107 against 1 906 TFLOP/s from registers, 1 755 against
+//                 1 630 re-read from LDS).  Alone 176 against 181 us on the 90-GF layer, 141 against 151 on 512 -> 512 @ 20x20x8; with
+//                 four scenes in flight, parent / 32 / 16 alternated: 541.9 / 545.9 / 551.8, 516.1 / 517.1 / 537.6 and 527.8 / 527.3 /
+//                 542.2 scenes/s in three jobs (profiles/r21_wz_mfma_shape.md) -> 16 on every Winograd layer
 //   split_target  interleaved A/B, tools/split_ab.py: 128 / 256 are 20-30 % slower on the stride-2 and 400-voxel layers, 1024+ no better
 //   halo_narrow   1 = 64-column tiles for layers with <= 64 output channels and 32-column tiles (8 x 1 waves) for <= 32; 64 = never
 //                 below 64 columns (the round-2..4 form, A/B); 0 = always 128
@@ -273,7 +278,7 @@ static int conv_finish(const ConvParams &p, int64_t OV, hipStream_t st) {
 // workspace a split launch accumulates with float atomics, and the 2-D forms, whose entry points carry none, take one split.
 static ConvPlan plan_conv(const ConvParams &p, int64_t OV, bool masked) {
   ConvPlan pl = {};
-  pl.family = kConvTile; pl.splitk = 1;
+  pl.family = kConvTile; pl.splitk = 1; pl.mfma = 32;
   const bool halo = g_tune_conv_halo && !p.transposed && p.ksize == 3 && p.stride == 1 && p.Cout >= g_tune_halo_min_cout;
   const bool narrow_n = g_tune_halo_narrow && p.Cout <= 64;          // 64-column tiles for layers with <= 64 output channels,
   const bool narrow_32 = g_tune_halo_narrow >= 1 && g_tune_halo_narrow != 64 && p.Cout <= 32;   // 32-column tiles (8 x 1 waves) for the head's 28 columns
@@ -307,6 +312,7 @@ static ConvPlan plan_conv(const ConvParams &p, int64_t OV, bool masked) {
     const bool small = fit2 && (!fit4 || g_tune_wz_brick == 2 || (g_tune_wz_brick == 0 && rows(2, 10, 10) < rows(4, 8, 8)));
     if (small) brick(kConvHaloWZ, 2, 10, 10, 128);
     else if (fit4) brick(kConvHaloWZ, 4, 8, 8, 128);
+    pl.mfma = g_tune_wz_mfma == 32 ? 32 : 16;
     if (pl.family == kConvHaloWZ && J % pl.bx != 0) pl.unsupported = "conv: a brick of the virtual Winograd stack must hold images of one position";
     else if (pl.family != kConvHaloWZ) pl.unsupported = "conv: the virtual Winograd stack needs Z / 2 = 2 or a multiple of 4 (and then halo_min_m stack rows) and > 64 output channels";
   } else if (halo && g_tune_halo_2d && p.two_d && p.wz_Z == 0 && p.M >= g_tune_halo_min_m && p.gy >= 8 && p.gz >= 8) {

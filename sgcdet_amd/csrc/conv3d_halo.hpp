@@ -27,9 +27,13 @@ namespace sgc {
 // BZ = 10 (the 2 images x 10 x 10 Winograd brick, 200 rows + 56 pad rows) has no such pitch: tools/halo_pitch_enum.py replays the
 // kernel's greedy assignment for the pitches 12..16 and counts the 16-lane ds_read_b128 groups (of 16) that keep a two-way
 // conflict -- 13, 7, 12, 13, 12 -- so 13 it is; the LDS plan is the 139 KB epilogue tile at every one of them.
-__host__ __device__ constexpr int halo_pitch(int BZ) { return BZ == 8 ? 12 : BZ == 10 ? 13 : BZ + 2; }
-__host__ __device__ constexpr size_t halo_tab_offset(int lrows, int mrows = 256, int bnv = 128) {
-  const size_t planes = (size_t)(2 * lrows + 2 * 2 * bnv) * LDKH * sizeof(uint16_t);   // A hi|lo + 2 x B hi|lo
+// MF = 16 (the Winograd bricks on v_mfma_f32_16x16x32_bf16, see the kernel): rows of 96 bytes, on which a 16-lane read group is
+// conflict-free iff each of its two 8-lane halves holds rows distinct mod 8.  A z run of 8 is that at any pitch (12 is kept);
+// BZ = 10 keeps 12, 10, 6, 12, 12 conflicting groups of 32 at the pitches 12..16 (halo_pitch_enum.py --mfma16) -- 14.
+__host__ __device__ constexpr int halo_pitch(int BZ, int MF = 32) { return BZ == 8 ? 12 : BZ == 10 ? (MF == 16 ? 14 : 13) : BZ + 2; }
+__host__ __device__ constexpr int halo_ldk(int MF) { return MF == 16 ? BK + 16 : LDKH; }   // bf16 per LDS row
+__host__ __device__ constexpr size_t halo_tab_offset(int lrows, int mrows = 256, int bnv = 128, int ldk = LDKH) {
+  const size_t planes = (size_t)(2 * lrows + 2 * 2 * bnv) * ldk * sizeof(uint16_t);   // A hi|lo + 2 x B hi|lo
   const size_t stage = (size_t)mrows * (bnv + 8) * sizeof(float);                      // epilogue tile [MROWS][BNV + 8]
   return planes > stage ? planes : stage;
 }
@@ -52,9 +56,17 @@ __host__ __device__ constexpr size_t halo_tab_offset(int lrows, int mrows = 256,
 // WZ (2-D form only): the image stack is VIRTUAL -- image k * J + j, pixel (xx, yy) is the Winograd F(2,3)-along-z input transform
 // t_k of the raw volume p.x [rows][cols][Z = 2 J][Cin] at the output pair j (sgc_conv3d_winograd_z_bf16x3): every staged chunk is
 // loaded from TWO voxel rows and combined (a - b, or a + b for k = 1) in front of the hi / lo split; no transformed copy exists.
-template <int BX, int BY, int BZ, int BNV = 128, int NP = 3, bool TD = false, bool STG = true, bool WZ = false>
+// MF (Winograd bricks only, `wz_mfma`): the MFMA shape, 32 = v_mfma_f32_32x32x16 as everywhere else, 16 = v_mfma_f32_16x16x32.  Same
+// waves, same 64 x 64 wave tile (4 x 4 tiles, sixteen 4-register accumulators), same staging, barriers and tap unrolling; a tap
+// is ONE k-step, so the two operand sets of the pipelined schedule are the A fragments of row tiles 0-1 and 2-3 over one set of B
+// fragments, refilled tile by tile behind the last MFMA that reads each.  What differs: the LDS rows are 96 bytes (halo_pitch), the
+// lane -> voxel table deals rows by residue mod 8, the weight rows a thread stages, the fragment reads, the product loop and the
+// accumulator -> LDS-tile store of the epilogue.  The instruction sums differently: last-bit differences against MF = 32.
+template <int BX, int BY, int BZ, int BNV = 128, int NP = 3, bool TD = false, bool STG = true, bool WZ = false, int MF = 32>
 __global__ __launch_bounds__(512) void conv3d_halo_bf16x3_kernel(const ConvParamsB p) {
   static_assert(!WZ || TD, "the virtual Winograd stack is a 2-D form");
+  static_assert(MF == 32 || (MF == 16 && WZ && STG && BNV == 128 && BX * BY * BZ <= 256), "the 16x16x32 form: pipelined Winograd bricks only");
+  constexpr int LDKH = halo_ldk(MF);                    // bf16 per LDS row (shadows the 80-byte rows of conv_common.hpp)
   constexpr int NTAP = TD ? 9 : 27, XO = TD ? 0 : 1;    // taps; halo width along x
   // MFMA rows of the brick: 256 for the standard bricks; a brick with another voxel count (a whole small grid: 10 x 10 x 4, the
   // coarsest config-2 scale) is padded to a multiple of 128 rows (4 wave rows x 32) -- pad rows work on voxel 0 and are dropped
@@ -67,7 +79,7 @@ __global__ __launch_bounds__(512) void conv3d_halo_bf16x3_kernel(const ConvParam
   static_assert(MROWS <= 512, "one table entry per thread");
   constexpr int TN = BNV / (32 * WNV), WCOL = BNV / WNV; // 32-column tiles per wave, columns per wave
   constexpr int HX = BX + 2 * XO, HY = BY + 2, HZ = BZ + 2, HROWS = HX * HY * HZ;
-  constexpr int HZP = halo_pitch(BZ), LROWS = HX * HY * HZP;   // z-pitch of the LDS image (see halo_pitch)
+  constexpr int HZP = halo_pitch(BZ, MF), LROWS = HX * HY * HZP;   // z-pitch of the LDS image (see halo_pitch)
   constexpr int NT = 512;
   constexpr int NA = (HROWS * 8 + NT - 1) / NT;     // float4 halo chunks per thread
   constexpr int A_PLANE = LROWS * LDKH, B_PLANE = BNV * LDKH;
@@ -75,7 +87,7 @@ __global__ __launch_bounds__(512) void conv3d_halo_bf16x3_kernel(const ConvParam
   __bf16 *A_hi = reinterpret_cast<__bf16 *>(smem_h), *A_lo = A_hi + A_PLANE;
   __bf16 *Bbase = A_lo + A_PLANE;                   // [2][hi|lo][BNV][LDKH]
   // [8 tiles][32 lanes], behind both the staging planes and the epilogue's output tile that later overlays them
-  unsigned short *vox_tab = reinterpret_cast<unsigned short *>(smem_h + halo_tab_offset(LROWS, MROWS, MROWS > 256 ? BNV : 128));
+  unsigned short *vox_tab = reinterpret_cast<unsigned short *>(smem_h + halo_tab_offset(LROWS, MROWS, MROWS > 256 ? BNV : 128, LDKH));
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid / WNV, wn = wid % WNV;
@@ -102,26 +114,40 @@ __global__ __launch_bounds__(512) void conv3d_halo_bf16x3_kernel(const ConvParam
   // One wave per tile, lane j = row j of the tile (both wave halves compute the same; the upper half does not store): a row whose
   // residue it is the first / second to carry takes slot residue / 16 + residue; further rows of a crowded residue fill the
   // slots of the residues that came short, in order.
+  // MF = 16: lane l of a 16-row tile reads chunk l >> 4 of row l & 15, so a 16-lane group holds eight rows at chunk c (lanes
+  // 0-3, 12-15 of the tile) and the other eight at chunk c + 1 (lanes 4-11).  On 96-byte rows a lane sits at (6 row + chunk) mod 16
+  // in 16-byte units -- the parity of its chunk -- so a group is conflict-free iff each half's rows are distinct mod 8, under any
+  // tap offset.  (On 80-byte rows no assignment is: 5 row takes every residue over a tile, and the chunk-(c + 1) half would have to
+  // map onto itself under + 1.)  The same greedy pass over 32 rows, then: residues mod 8, four halves (two 16-row tiles), the row
+  // that is the k-th to carry its residue goes to half k.
+  constexpr int RES = MF == 16 ? 8 : 16, RANKS = 32 / RES;           // residues; rows per residue a 32-row table segment seats
+  const auto seat = [](int k, int q) {                               // slot of the k-th row with residue q
+    if constexpr (MF == 16) return (k >> 1) * 16 + ((k & 1) ? 4 + q : q < 4 ? q : q + 8);
+    else return k * 16 + q;
+  };
   for (int t = wid; t < MROWS / 32; t += NT / 64) {
     const int j = lane & 31;
     const int r = t * 32 + j, rv = r < NVOX ? r : 0;
     const int x = rv / (BY * BZ), y = (rv / BZ) % BY, z = rv % BZ;
-    const int res = (((x + XO) * HY + (y + 1)) * HZP + (z + 1)) & 15;
-    unsigned same = 0, mine = 0;                      // rows with this row's residue / with this SLOT's residue (slot j: j & 15)
+    const int res = (((x + XO) * HY + (y + 1)) * HZP + (z + 1)) & (RES - 1);
+    // what slot j seats: residue sq, rank sk (MF = 32: j & 15, j >> 4)
+    const int ji = j & 15, jb = MF == 16 && ji >= 4 && ji < 12;
+    const int sq = MF == 16 ? (jb ? ji - 4 : ji < 4 ? ji : ji - 8) : ji, sk = MF == 16 ? 2 * (j >> 4) + jb : j >> 4;
+    unsigned same = 0, mine = 0;                      // rows with this row's residue / with this SLOT's residue
 #pragma unroll
-    for (int q = 0; q < 16; ++q) {
+    for (int q = 0; q < RES; ++q) {
       const unsigned m = (unsigned)__ballot(res == q);
       if (res == q) same = m;
-      if ((j & 15) == q) mine = m;
+      if (sq == q) mine = m;
     }
     const unsigned below = (1u << j) - 1u;
     const int rank = __popc(same & below);
-    const bool slot_empty = __popc(mine) < (j >> 4) + 1;
-    const unsigned left = (unsigned)__ballot(rank >= 2), empty = (unsigned)__ballot(slot_empty);
+    const bool slot_empty = __popc(mine) < sk + 1;
+    const unsigned left = (unsigned)__ballot(rank >= RANKS), empty = (unsigned)__ballot(slot_empty);
     const unsigned short val = r < NVOX ? (unsigned short)r : kPadRow;
     unsigned short *tab = vox_tab + t * 32, *tmp = vox_tab + MROWS + (wid & 7) * 32;
     if (lane < 32) {
-      if (rank < 2) tab[rank * 16 + res] = val;
+      if (rank < RANKS) tab[seat(rank, res)] = val;
       else tmp[__popc(left & below)] = val;
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // one wave, LDS operations complete in order: its own stores are visible
@@ -129,10 +155,14 @@ __global__ __launch_bounds__(512) void conv3d_halo_bf16x3_kernel(const ConvParam
   }
   __syncthreads();
   const int fr = lane & 31, fh = lane >> 5;
-  int arow[RT];
+  // MF = 16: RT16 row tiles and TN16 column tiles of 16 per wave; lane = row / column fr16 of a tile, chunk fq of its 32 channels
+  constexpr int RT16 = 2 * RT, TN16 = BNV / (16 * WNV);
+  const int fr16 = lane & 15, fq = lane >> 4;
+  int arow[MF == 16 ? RT16 : RT];
 #pragma unroll
-  for (int i = 0; i < RT; ++i) {
-    const int r = vox_tab[(wm * RT + i) * 32 + fr] & 0x7fff;          // pad rows read voxel 0's halo rows (valid LDS, result dropped)
+  for (int i = 0; i < (MF == 16 ? RT16 : RT); ++i) {
+    // pad rows read voxel 0's halo rows (valid LDS, result dropped)
+    const int r = (MF == 16 ? vox_tab[wm * RT * 32 + i * 16 + fr16] : vox_tab[(wm * RT + i) * 32 + fr]) & 0x7fff;
     const int x = r / (BY * BZ), y = (r / BZ) % BY, z = r % BZ;
     arow[i] = ((x + XO) * HY + (y + 1)) * HZP + (z + 1);
   }
@@ -174,16 +204,25 @@ __global__ __launch_bounds__(512) void conv3d_halo_bf16x3_kernel(const ConvParam
   // B staging slot of this thread: 8 bf16 at (tid&3)*8 of row bn; the 16 lanes of one ds_write_b128 pass take rows
   // {r, r+4, r+8, r+12} (16 banks apart at the 20-dword pitch) instead of 4 consecutive rows that overlap by 12 banks
   const int bc = tid & 3, rs16 = (tid >> 2) & 15;
-  const int bn = 16 * wid + (rs16 >> 2) + 4 * (rs16 & 3);
+  // (96-byte rows, MF = 16: rows {r, r+2, r+4, r+6} are 16 banks apart at the 24-dword pitch)
+  const int bn = MF == 16 ? 16 * wid + 2 * (rs16 & 3) + ((rs16 >> 2) & 1) + 8 * (rs16 >> 3) : 16 * wid + (rs16 >> 2) + 4 * (rs16 & 3);
   const bool bn_ok = tid < BNV * 4 && n0 + bn < p.Cout;     // BNV * 4 sixteen-byte chunks per plane and tap
 
-  f32x16 acc[RT][TN];
+  // MF = 32: acc; MF = 16: acc16 (the other is one unused element)
+  f32x16 acc[MF == 16 ? 1 : RT][MF == 16 ? 1 : TN];
+  f32x4 acc16[MF == 16 ? RT16 : 1][MF == 16 ? TN16 : 1];
 #pragma unroll
-  for (int i = 0; i < RT; ++i)
+  for (int i = 0; i < (MF == 16 ? 1 : RT); ++i)
 #pragma unroll
-    for (int j = 0; j < TN; ++j)
+    for (int j = 0; j < (MF == 16 ? 1 : TN); ++j)
 #pragma unroll
       for (int k = 0; k < 16; ++k) acc[i][j][k] = 0.f;
+#pragma unroll
+  for (int i = 0; i < (MF == 16 ? RT16 : 1); ++i)
+#pragma unroll
+    for (int j = 0; j < (MF == 16 ? TN16 : 1); ++j)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) acc16[i][j][k] = 0.f;
   SGC_HALO_STAMP(0);
 
   float4 ra[NA], rw[WZ ? NA : 1];      // rw: the second voxel row of a Winograd transform chunk
@@ -318,11 +357,92 @@ __global__ __launch_bounds__(512) void conv3d_halo_bf16x3_kernel(const ConvParam
 #pragma unroll
       for (int j = 0; j < TN; ++j) acc[i][j] = mma_split<NP>(f.ah[i], f.al[i], f.bh[j], f.bl[j], acc[i][j]);
   };
+  // MF = 16: a tap is one k-step.  A fragments of two of the wave's four row tiles (one half of the tap), B fragments of its column tiles
+  struct FragA16 { bf16x8 h[2], l[2]; };
+  struct FragB16 { bf16x8 h[TN16], l[TN16]; };
+  auto read_A16 = [&](FragA16 &f, int toff, int half) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int o = (arow[MF == 16 ? 2 * half + i : 0] + toff) * LDKH + fq * 8;
+      f.h[i] = *reinterpret_cast<const bf16x8 *>(A_hi + o);
+      if constexpr (NP == 3) f.l[i] = *reinterpret_cast<const bf16x8 *>(A_lo + o);
+    }
+  };
+  auto read_B16 = [&](FragB16 &f, int buf, int j) {
+    const __bf16 *b = Bbase + buf * 2 * B_PLANE + (wn * WCOL + j * 16 + fr16) * LDKH + fq * 8;
+    f.h[j] = *reinterpret_cast<const bf16x8 *>(b);
+    if constexpr (NP == 3) f.l[j] = *reinterpret_cast<const bf16x8 *>(b + B_PLANE);
+  };
+  // one half of a tap: column tile by column tile, the three products interleaved over the two row tiles (no accumulator waits
+  // on its own previous MFMA; each still sees lo*hi, hi*lo, hi*hi of a tap in this order).  next_buf >= 0: the fragments of
+  // column tile j are refilled from that weight buffer behind the last MFMA that reads them
+  auto mfma16_half = [&](const FragA16 &a, int half, FragB16 &b, int next_buf) {
+#pragma unroll
+    for (int j = 0; j < TN16; ++j) {
+      f32x4 &c0 = acc16[MF == 16 ? 2 * half : 0][MF == 16 ? j : 0], &c1 = acc16[MF == 16 ? 2 * half + 1 : 0][MF == 16 ? j : 0];
+      c0 = mma_split_one<NP, 0>(a.h[0], a.l[0], b.h[j], b.l[j], c0);
+      c1 = mma_split_one<NP, 0>(a.h[1], a.l[1], b.h[j], b.l[j], c1);
+      c0 = mma_split_one<NP, 1>(a.h[0], a.l[0], b.h[j], b.l[j], c0);
+      c1 = mma_split_one<NP, 1>(a.h[1], a.l[1], b.h[j], b.l[j], c1);
+      c0 = mma_split_one<NP, 2>(a.h[0], a.l[0], b.h[j], b.l[j], c0);
+      c1 = mma_split_one<NP, 2>(a.h[1], a.l[1], b.h[j], b.l[j], c1);
+      if (next_buf >= 0) read_B16(b, next_buf, j);
+    }
+  };
   const int steps_total = (c_hi - c_lo) * NTAP;
   auto step_tap = [&](int st) { return st % NTAP; };
   auto step_cc = [&](int st) { return c_lo + st / NTAP; };
 
-  if constexpr (STG) {
+  if constexpr (MF == 16) {
+    // The pipelined schedule below with P / Q = the A fragments of row tiles 0-1 / 2-3 (16 registers each) and ONE set of B fragments
+    // (32 registers).  Tap g, every wave:
+    //   first half   issue the reads of Q(g); write the weight tile of tap g + 1, start the load of tap g + 2; multiply P(g) by B(g)
+    //   BARRIER      publishes tile g + 1
+    //   second half  issue the reads of P(g + 1); multiply Q(g) by B(g), refilling each column tile's fragments with B(g + 1)
+    // Hazards as below: tile g + 1 overwrites tile g - 1, whose reads (the refills of tap g - 2's second half) completed before
+    // barrier g - 1; the refills follow barrier g.  A slice's last tap reads neither the halo image nor the weights in its second half.
+    load_A(c_lo);
+    load_B(0, c_lo);
+    split_A();
+    store_A();
+    store_B(0);
+    if (steps_total > 1) load_B(step_tap(1), step_cc(1));
+    __syncthreads();
+    FragA16 P = {}, Q = {};
+    FragB16 B = {};
+    if (wave_live) {
+      read_A16(P, tap_off(0), 0);
+#pragma unroll
+      for (int j = 0; j < TN16; ++j) read_B16(B, 0, j);
+    }
+    int g = 0;
+    for (int cc = c_lo; cc < c_hi; ++cc) {
+#pragma unroll
+      for (int tap = 0; tap < NTAP; ++tap, ++g) {
+        const bool last_tap = tap == NTAP - 1;
+        if (wave_live) read_A16(Q, tap_off(tap), 1);
+        if (g + 1 < steps_total) store_B((g + 1) & 1);
+        if (g + 2 < steps_total) load_B(step_tap(g + 2), step_cc(g + 2));
+        if (tap == NTAP - 3 && cc + 1 < c_hi) load_A(cc + 1);
+        if (wave_live) mfma16_half(P, 0, B, -1);
+        if (last_tap && cc + 1 < c_hi) split_A();
+        __syncthreads();
+        __builtin_amdgcn_sched_barrier(0);
+        if (wave_live && !last_tap) read_A16(P, tap_off(tap + 1), 0);
+        if (last_tap && cc + 1 < c_hi) store_A();
+        if (wave_live) mfma16_half(Q, 1, B, last_tap ? -1 : (g + 1) & 1);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      if (cc + 1 < c_hi) {
+        __syncthreads();                                          // the new halo image is published
+        if (wave_live) {
+          read_A16(P, tap_off(0), 0);
+#pragma unroll
+          for (int j = 0; j < TN16; ++j) read_B16(B, g & 1, j);
+        }
+      }
+    }
+  } else if constexpr (STG) {
     // P: operands of a tap's first k-half, Q: of its second k-half (32 registers each).  Tap g, every wave:
     //   first half   issue the reads of Q(g); write the weight tile of tap g + 1 (registers loaded during tap g - 1) and
     //                start the load of tap g + 2; multiply P(g) -- in registers since the second half of tap g - 1
@@ -425,9 +545,19 @@ __global__ __launch_bounds__(512) void conv3d_halo_bf16x3_kernel(const ConvParam
   // Epilogue through LDS (as in the implicit-GEMM kernel): the halo / weight buffers are free, the 256 x 128 tile
   // leaves as 16-byte row-contiguous stores instead of 64 four-byte stores per lane.
   if ((p.Cout & 3) == 0 && (p.splitk == 1 || p.ws)) {
-    constexpr int LDC = BNV + 8;
+    // (MF = 16: a lane quarter sits 4 rows below the previous one, and 4 rows of BNV + 4 floats are 16 banks)
+    constexpr int LDC = MF == 16 ? BNV + 4 : BNV + 8;
     float *cs = reinterpret_cast<float *>(smem_h);           // [MROWS][LDC] floats (139 KB for 256 x 128; launch_halo sizes LDS for it)
     if constexpr (STG) __syncthreads();                      // the second half of the last tap ran after the loop's last barrier
+    if constexpr (MF == 16) {
+#pragma unroll
+      for (int i = 0; i < RT16; ++i)
+#pragma unroll
+        for (int j = 0; j < TN16; ++j)
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+            cs[(wm * (RT * 32) + i * 16 + acc16_row(lane) + k) * LDC + wn * WCOL + j * 16 + fr16] = acc16[i][j][k];
+    } else {
 #pragma unroll
     for (int i = 0; i < RT; ++i)
 #pragma unroll
@@ -435,6 +565,7 @@ __global__ __launch_bounds__(512) void conv3d_halo_bf16x3_kernel(const ConvParam
 #pragma unroll
         for (int k = 0; k < 16; ++k)
           cs[(wm * (RT * 32) + i * 32 + (k & 3) + 8 * (k >> 2) + 4 * (lane >> 5)) * LDC + wn * WCOL + j * 32 + (lane & 31)] = acc[i][j][k];
+    }
     __syncthreads();
     constexpr int C4 = BNV / 4;
     for (int e = tid; e < MROWS * C4; e += NT) {
@@ -471,6 +602,37 @@ __global__ __launch_bounds__(512) void conv3d_halo_bf16x3_kernel(const ConvParam
     return;
   }
 
+  // element-wise stores (Cout % 4 != 0, or a split without a workspace): one accumulator element at a time, by the shape's map
+  const auto store_one = [&](int tab_row, int col, float sc, float sh, float a) {
+    const int r = vox_tab[tab_row];
+    const int x = X0 + r / (BY * BZ), y = Y0 + (r / BZ) % BY, z = Z0 + r % BZ;
+    if ((r & kPadRow) || x >= p.gx || y >= p.gy || z >= p.gz) return;
+    const int64_t orow = ((int64_t)x * p.gy + y) * p.gz + z;
+    float *dst = p.y + orow * p.Cout + col;
+    if (p.splitk > 1) {
+      if (p.ws) p.ws[(int64_t)blockIdx.z * p.ws_stride + orow * p.Cout + col] = a;
+      else atomicAdd(dst, a);
+    } else {
+      float v = a * sc + sh;
+      if (p.relu == 2) v = relu_nan(v);
+      if (p.residual) v += p.residual[orow * p.Cout + col];
+      if (p.relu == 1) v = relu_nan(v);
+      if (p.act_scale) v = act_col(v, col, p.act_c0, p.act_c1, *p.act_scale);
+      *dst = v;
+    }
+  };
+  if constexpr (MF == 16) {
+#pragma unroll
+    for (int i = 0; i < RT16; ++i)
+#pragma unroll
+      for (int j = 0; j < TN16; ++j) {
+        const int col = n0 + wn * WCOL + j * 16 + fr16;
+        if (col >= p.Cout) continue;
+        const float sc = p.scale ? p.scale[col] : 1.f, sh = p.shift ? p.shift[col] : 0.f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) store_one(wm * RT * 32 + i * 16 + acc16_row(lane) + k, col, sc, sh, acc16[i][j][k]);
+      }
+  } else {
 #pragma unroll
   for (int i = 0; i < RT; ++i)
 #pragma unroll
@@ -498,36 +660,39 @@ __global__ __launch_bounds__(512) void conv3d_halo_bf16x3_kernel(const ConvParam
         }
       }
     }
+  }
 }
 
 // Forms of this kernel that were built, bit-identical, and measured slower or equal (the code is in the
 // history up to round 3): weights by LDS-DMA into a four-stage ring with swizzled unpadded rows (237 vs 230 us warm on the 90-GF
 // layer); weights straight from L2 into registers, no barrier per tap (236 vs 229-240, 2-7 % slower elsewhere); three weight
-// buffers staged two taps ahead (236 vs 232); v_mfma_f32_16x16x32_bf16 (234 vs 230); a one-wave-per-SIMD form with 512
+// buffers staged two taps ahead (236 vs 232); v_mfma_f32_16x16x32_bf16 (234 vs 230: a timing build of round 2's lockstep kernel,
+// one stream, ranked by wall alone -- measured again as a correct kernel on the Winograd bricks with scenes in flight, where it
+// wins and is the default: MF = 16 above, profiles/r21_wz_mfma_shape.md); a one-wave-per-SIMD form with 512
 // registers (309 vs 251).  Round 6, Winograd (2-D, 9 taps per slice) form: the next slice's halo loads issued at the slice's second tap
 // and split two chunks per tap under the last four taps instead of one split under the last tap -- 191.5 vs 191.2 us on the 90-GF layer,
 // 155.8 vs 151.8 on 512 -> 512 @ 20x20x8 (profiles/r06_wz_skip.txt: the 13 us the restaging costs are not vector-issue time).
 
 // one launch of the form a plan names; p.splitk is the caller's (plan_conv and the launch-time downgrades of conv3d_bf16x3)
-template <int BX, int BY, int BZ, int BNV, int NP, bool TD, bool STG, bool WZ = false>
+template <int BX, int BY, int BZ, int BNV, int NP, bool TD, bool STG, bool WZ = false, int MF = 32>
 static int launch_halo_k(ConvParamsB &p, hipStream_t st) {
 #if defined(SGC_HALO_STAMPS)
   p.stamps = g_halo_stamp_buf;
 #endif
-  constexpr int LROWS = (TD ? BX : BX + 2) * (BY + 2) * halo_pitch(BZ);
+  constexpr int LROWS = (TD ? BX : BX + 2) * (BY + 2) * halo_pitch(BZ, MF);
   constexpr int RGRAN = BNV >= 64 ? 128 : 256;          // rows per (wave rows x 32): see the kernel's wave layout
   constexpr int MROWS = (BX * BY * BZ + RGRAN - 1) / RGRAN * RGRAN;
-  const size_t smem = halo_tab_offset(LROWS, MROWS, MROWS > 256 ? BNV : 128) + (MROWS + 256) * sizeof(uint16_t);   // table + 8 x 32 scratch
-  static_assert(halo_tab_offset(LROWS, MROWS, MROWS > 256 ? BNV : 128) + (MROWS + 256) * sizeof(uint16_t) <= 160 * 1024, "brick does not fit the LDS");
+  const size_t smem = halo_tab_offset(LROWS, MROWS, MROWS > 256 ? BNV : 128, halo_ldk(MF)) + (MROWS + 256) * sizeof(uint16_t);   // table + 8 x 32 scratch
+  static_assert(halo_tab_offset(LROWS, MROWS, MROWS > 256 ? BNV : 128, halo_ldk(MF)) + (MROWS + 256) * sizeof(uint16_t) <= 160 * 1024, "brick does not fit the LDS");
   static std::atomic<uint64_t> attr_done{0};
-  ensure_dynamic_lds((const void *)conv3d_halo_bf16x3_kernel<BX, BY, BZ, BNV, NP, TD, STG, WZ>, (int)smem, attr_done);
+  ensure_dynamic_lds((const void *)conv3d_halo_bf16x3_kernel<BX, BY, BZ, BNV, NP, TD, STG, WZ, MF>, (int)smem, attr_done);
   const int bricks = ceil_div(p.gx, BX) * ceil_div(p.gy, BY) * ceil_div(p.gz, BZ);
   const int nb = ceil_div(p.Cout, BNV);
-  hipLaunchKernelGGL((conv3d_halo_bf16x3_kernel<BX, BY, BZ, BNV, NP, TD, STG, WZ>), dim3(bricks, nb, p.splitk), dim3(512), smem, st, p);
+  hipLaunchKernelGGL((conv3d_halo_bf16x3_kernel<BX, BY, BZ, BNV, NP, TD, STG, WZ, MF>), dim3(bricks, nb, p.splitk), dim3(512), smem, st, p);
   return check_launch("conv3d_halo_bf16x3_kernel");
 }
 
-template <int BX, int BY, int BZ, int BNV = 128, bool TD = false, bool WZ = false>
+template <int BX, int BY, int BZ, int BNV = 128, bool TD = false, bool WZ = false, int MF = 32>
 static int launch_halo(ConvParamsB &p, hipStream_t st) {
   // the one-product modes and the Winograd stack: the software-pipelined form only.  (sgc_set_conv_products admits 1, 2 and 3 and
   // nothing else: any other value would select the pipelined NP = 3 form here, where the old ladder fell through to the lines below.)
@@ -540,7 +705,7 @@ static int launch_halo(ConvParamsB &p, hipStream_t st) {
       return launch_halo_k<BX, BY, BZ, BNV, 3, TD, true>(p, st);
     }
   }
-  return with_products(g_conv_products, [&](auto np) { return launch_halo_k<BX, BY, BZ, BNV, np(), TD, true, WZ>(p, st); });
+  return with_products(g_conv_products, [&](auto np) { return launch_halo_k<BX, BY, BZ, BNV, np(), TD, true, WZ, MF>(p, st); });
 }
 
 int launch_halo_z4(ConvParamsB &p, const ConvPlan &pl, hipStream_t st);   // conv3d_halo_z4.hip

@@ -4,6 +4,8 @@
 
 namespace sgc {
 int launch_halo_2d(ConvParamsB &p, const ConvPlan &pl, hipStream_t st) {
+  if (pl.family == kConvHaloWZ && pl.mfma == 16)      // the Winograd bricks on v_mfma_f32_16x16x32 (`wz_mfma`)
+    return pl.bx == 2 ? launch_halo<2, 10, 10, 128, true, true, 16>(p, st) : launch_halo<4, 8, 8, 128, true, true, 16>(p, st);
   if (pl.family == kConvHaloWZ)
     return pl.bx == 2 ? launch_halo<2, 10, 10, 128, true, true>(p, st) : launch_halo<4, 8, 8, 128, true, true>(p, st);
   if (pl.bx == 4) return launch_halo<4, 8, 8, 128, true>(p, st);

@@ -84,6 +84,7 @@ struct ConvPlan {
   ConvFamily family;        // row GEMM | halo bricks | whole-grid halo brick | 2-D halo form | its virtual Winograd stack | tile kernel
   int bx, by, bz;           // halo families: the brick
   int bn;                   // columns per workgroup tile: 32 | 64 | 128
+  int mfma;                 // Winograd stack: the MFMA shape of its bricks, 32 (32x32x16, as every other family) | 16 (16x16x32)
   int splitk, steps_per;    // reduction splits; tile kernel: K steps per split (ConvParams.steps_per)
   int64_t ws_floats;        // split-K workspace this choice needs for a deterministic sum (0: one split)
   const char *unsupported;  // non-null: no kernel takes the call, and why

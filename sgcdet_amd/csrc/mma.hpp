@@ -74,6 +74,35 @@ __device__ __forceinline__ f32x16 mma_split(const bf16x8 &ah, const bf16x8 &al, 
   return mma_hh<NP>(ah, bh, c);
 }
 
+// The same on v_mfma_f32_16x16x32_bf16 / _f16 (the Winograd bricks of the halo kernel under `wz_mfma` = 16; conv3d_halo.hpp).
+// Operands: lane l holds row (A) or column (B) l & 15 and the eight k = 8 (l >> 4) .. + 7 -- a 32-channel slice is ONE k-step, and
+// a lane reads the 16-byte chunk l >> 4 of its row.  16x16 accumulator: 4 floats, lane = column l & 15, rows acc16_row(l) .. + 3.
+// The instruction sums 32 products where the 32x32x16 form sums 16 twice: results differ from that form in the last bits.
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+__host__ __device__ constexpr int acc16_row(int lane) { return 4 * (lane >> 4); }
+template <int NP>
+__device__ __forceinline__ f32x4 mma_hh(bf16x8 a, bf16x8 b, f32x4 c) {
+  if constexpr (NP == 2)
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+  else
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
+// one product of the mode (0: lo*hi, 1: hi*lo, 2: hi*hi) -- the caller interleaves the accumulators of a tile row, so that none
+// waits for its own previous MFMA, and keeps this order per accumulator; the one-product modes have product 2 only
+template <int NP, int PROD>
+__device__ __forceinline__ f32x4 mma_split_one(const bf16x8 &ah, const bf16x8 &al, const bf16x8 &bh, const bf16x8 &bl, f32x4 c) {
+  if constexpr (PROD == 2) return mma_hh<NP>(ah, bh, c);
+  else if constexpr (NP != 3) return c;
+  else if constexpr (PROD == 0) return __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, c, 0, 0, 0);
+  else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, c, 0, 0, 0);
+}
+template <int NP>
+__device__ __forceinline__ f32x4 mma_split(const bf16x8 &ah, const bf16x8 &al, const bf16x8 &bh, const bf16x8 &bl, f32x4 c) {
+  c = mma_split_one<NP, 0>(ah, al, bh, bl, c);
+  c = mma_split_one<NP, 1>(ah, al, bh, bl, c);
+  return mma_split_one<NP, 2>(ah, al, bh, bl, c);
+}
+
 // host: the process-wide mode (g_conv_products) as the compile-time NP of a launch -- f(std::integral_constant<int, NP>)
 template <class F>
 inline auto with_products(int products, F &&f) {

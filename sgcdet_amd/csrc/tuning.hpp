@@ -1,5 +1,6 @@
 // The tuning knobs of the library (sgc_set_tuning, SGC_TUNE): ONE line per knob -- key, variable, default, meaning.
-// Results never depend on a knob (the *_diag ones excepted, which are inert without SGC_DIAG=1).  The variables are defined,
+// Results never depend on a knob (the *_diag ones excepted, which are inert without SGC_DIAG=1, and wz_mfma, whose two values
+// differ in the last bits: the instruction sums differently; each value is deterministic).  The variables are defined,
 // and the keys looked up, in api.hip; why a default is what it is (A/B numbers, profiles/) is recorded next to the code that
 // reads the knob.  Adding or retiring a knob is one line here.
 #pragma once
@@ -35,6 +36,7 @@
   X("halo_narrow", g_tune_halo_narrow, 1, "1: 64- and 32-column tiles for few output channels, 64: never below 64, 0: 128")  \
   X("halo_2d", g_tune_halo_2d, 1, "3x3 layers over an image stack: 1 bricks of 16 x 16 pixels, 2 of 4 images x 8 x 8, 0 tile kernel") \
   X("wz_brick", g_tune_wz_brick, 0, "Winograd-z stack: 0 the brick with fewer matrix rows, 1: 4 images x 8 x 8, 2: 2 images x 10 x 10 (where each fits)") \
+  X("wz_mfma", g_tune_wz_mfma, 16, "Winograd-z bricks: MFMA shape, 16 = 16x16x32, 32 = 32x32x16 (last-bit differences; each value deterministic)") \
   X("halo_split_target", g_tune_halo_split_target, 192, "halo kernel: channel slices are split until a launch has this many workgroups") \
   X("halo_wave_fix", g_tune_halo_wave_fix, 1, "one more split on a small CU overflow: 1 latency geometry only, 2 always")    \
   X("split_target", g_tune_split_target, 512, "tile kernel: the reduction is split until a launch has this many workgroups") \
