@@ -7,7 +7,8 @@ points of ``include/sgcdet_amd_train.h`` have a table of their own
 (``TRAIN_SIGNATURES`` / ``TRAIN_INTROSPECTION``), bound only when ``Library`` is
 asked for it (the product library; the oracle has no twin of them); the image-side
 convolutions of ``include/sgcdet_amd_image.h`` likewise (``IMAGE_SIGNATURES`` /
-``IMAGE_INTROSPECTION``).  Nothing
+``IMAGE_INTROSPECTION``); ``include/sgcdet_amd_depth_train.h`` (``DEPTH_TRAIN_SIGNATURES`` /
+``DEPTH_TRAIN_INTROSPECTION``) is bound together with the training tables.  Nothing
 here touches torch; pointers are plain integers (``tensor.data_ptr()``).
 """
 import ctypes as C
@@ -126,6 +127,16 @@ TRAIN_INTROSPECTION = {
     "sgc_conv2d_stem7_wgrad_workspace_floats": (C.c_int64, [_i] * 3),
 }
 
+# include/sgcdet_amd_depth_train.h: the padded live BatchNorm and the softmax backward of the depth net's U-Nets and depth_reg in
+# training (no CPU-oracle twin; bound with the training tables)
+DEPTH_TRAIN_SIGNATURES = {
+    "sgc_bn_rows_padded_forward": [_p] * 5 + [_f, _f] + [_p, _i] + [_p] * 4 + [C.c_int64, _i, _i, _i, _p],
+    "sgc_bn_rows_padded_backward": [_p] * 11 + [_i, _p, C.c_int64, _i, _i, _i, _p],
+    "sgc_softmax_rows_backward": [_p] * 3 + [C.c_int64] + [_i] * 4 + [_p],
+}
+
+DEPTH_TRAIN_INTROSPECTION = {}      # the padded norm sizes its workspace with sgc_bn_rows_workspace_floats (INTROSPECTION)
+
 # include/sgcdet_amd_image.h: the 2-D convolutions of the image-side CNNs (no CPU-oracle twin)
 IMAGE_SIGNATURES = {
     "sgc_conv2d_nhwc_ex_bf16x3": [_p] * 7 + [_i] * 13 + [_p],
@@ -163,13 +174,15 @@ class Library:
     """A loaded shared object exporting the sgcdet_amd C ABI."""
 
     def __init__(self, path, train=False, image=False):
-        """``train`` / ``image``: also bind (and require) the entry points of include/sgcdet_amd_train.h /
-        include/sgcdet_amd_image.h."""
+        """``train`` / ``image``: also bind (and require) the entry points of include/sgcdet_amd_train.h and
+        include/sgcdet_amd_depth_train.h / of include/sgcdet_amd_image.h."""
         self.path = str(path)
         self._dll = C.CDLL(self.path)
         missing = []
-        signatures = {**SIGNATURES, **(TRAIN_SIGNATURES if train else {}), **(IMAGE_SIGNATURES if image else {})}
-        introspection = {**INTROSPECTION, **(TRAIN_INTROSPECTION if train else {}), **(IMAGE_INTROSPECTION if image else {})}
+        signatures = {**SIGNATURES, **(TRAIN_SIGNATURES if train else {}), **(DEPTH_TRAIN_SIGNATURES if train else {}),
+                      **(IMAGE_SIGNATURES if image else {})}
+        introspection = {**INTROSPECTION, **(TRAIN_INTROSPECTION if train else {}), **(DEPTH_TRAIN_INTROSPECTION if train else {}),
+                         **(IMAGE_INTROSPECTION if image else {})}
         for name, argtypes in signatures.items():
             try:
                 fn = getattr(self._dll, name)

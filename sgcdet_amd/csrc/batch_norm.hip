@@ -5,11 +5,14 @@
 //                          workgroups in a FIXED order: the same bits every run), the running-statistics update of
 //                          nn.BatchNorm (unbiased variance, momentum), y = (x - mean) * invstd * weight + bias.
 //   sgc_bn_rows_backward   dweight = sum dy * xhat, dbias = sum dy, dx = weight * invstd * (dy - dbias / rows - xhat * dweight / rows).
+//   sgc_bn_rows_padded_*   the same over rows of pitch ld >= C with zero padding behind the channels, and the tail relu(bn) + residual
+//                          (include/sgcdet_amd_depth_train.h: the regulation U-Nets of DepthNet_Fusion in training).
 //
 // Round 2 ran torch's channels-last batch-norm kernels here: 43 us (statistics) + 52 us (backward reduction) per layer for
 // 26 MB tensors, 1.5 ms of a 25 ms training step.  These are plain column reductions: a workgroup walks a slab of rows with
 // 16-byte loads (a thread owns 4 channels), partial results meet in a small workspace.
 #include "common.hpp"
+#include "../../include/sgcdet_amd_depth_train.h"
 
 namespace sgc {
 
@@ -223,6 +226,193 @@ __global__ __launch_bounds__(BN_T) void bn_bwd_apply_kernel(const float4 *__rest
   }
 }
 
+// ---- the padded form (sgc_bn_rows_padded_forward / _backward, include/sgcdet_amd_depth_train.h) ----------------
+// Rows of pitch ld >= C: columns [C, ld) of the inputs are never read, those of the outputs are written as +0.0.  Statistics,
+// parameters and the workspace stay [C] wide, so the two final kernels above serve both forms.  For ld == C and tails 0 / 1 every
+// value below is computed by the expression, and in the order, of the dense kernels: the same bits.
+//   tail 0: y = bn(x) + residual?      tail 1: y = relu(bn(x) + residual?)      tail 2: y = relu(bn(x)) + residual
+
+// bn(x) of one element, spelled out as the dense apply kernel is compiled (subtract, multiply, one fused multiply-add): the forward
+// and the tail-2 backward, which recomputes its gate from it, evaluate exactly this
+__device__ __forceinline__ float bn_value(float v, float m, float s, float w, float b) {
+  return __fmaf_rn(__fmul_rn(__fsub_rn(v, m), s), w, b);
+}
+
+// dx of one element, likewise spelled out as the dense backward apply kernel is compiled:
+// weight * invstd * (g - dbias / rows - xhat * dweight / rows) with the two subtractions as fused multiply-adds
+__device__ __forceinline__ float bn_dx(float v, float g, float m, float is, float w, float db, float dw, float inv_rows) {
+  const float xhat = __fmul_rn(__fsub_rn(v, m), is);
+  const float t = __fmaf_rn(-inv_rows, __fmul_rn(xhat, dw), __fmaf_rn(-inv_rows, db, g));
+  return __fmul_rn(__fmul_rn(w, is), t);
+}
+
+__global__ __launch_bounds__(BN_T) void bnp_stats_partial_kernel(const float *__restrict__ x, float *__restrict__ ws, int rows, int C, int ld,
+                                                                 int rows_per_slab) {
+  extern __shared__ float bn_lds[];                    // [RL][CG * 4][3]
+  const int C4 = C >> 2;
+  const int CG = C4 < BN_T ? C4 : BN_T;
+  const int RL = BN_T / CG;
+  const int tid = threadIdx.x, cg = tid % CG, rl = tid / CG;
+  const int r_lo = blockIdx.x * rows_per_slab, r_hi = min(rows, r_lo + rows_per_slab);
+  for (int c0 = 0; c0 < C4; c0 += CG) {
+    const int c4 = c0 + cg;
+    float n = 0.f, mean[4] = {0.f, 0.f, 0.f, 0.f}, M2[4] = {0.f, 0.f, 0.f, 0.f};
+    if (c4 < C4 && rl < RL) {
+      for (int r = r_lo + rl; r < r_hi; r += RL) {
+        const float4 v4 = *reinterpret_cast<const float4 *>(x + (int64_t)r * ld + c4 * 4);
+        const float v[4] = {v4.x, v4.y, v4.z, v4.w};
+        n += 1.f;
+        const float inv = __frcp_rn(n);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float d = v[e] - mean[e];
+          mean[e] += d * inv;
+          M2[e] += d * (v[e] - mean[e]);
+        }
+      }
+    }
+    if (rl < RL && c4 < C4) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        bn_lds[((rl * CG + cg) * 4 + e) * 3 + 0] = n;
+        bn_lds[((rl * CG + cg) * 4 + e) * 3 + 1] = mean[e];
+        bn_lds[((rl * CG + cg) * 4 + e) * 3 + 2] = M2[e];
+      }
+    }
+    __syncthreads();
+    if (rl == 0 && c4 < C4) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float na = n, ma = mean[e], Ma = M2[e];
+        for (int l = 1; l < RL; ++l) {
+          const float *q = bn_lds + ((l * CG + cg) * 4 + e) * 3;
+          chan_merge(na, ma, Ma, q[0], q[1], q[2]);
+        }
+        ws[((int64_t)blockIdx.x * 2 + 0) * C + c4 * 4 + e] = ma;
+        ws[((int64_t)blockIdx.x * 2 + 1) * C + c4 * 4 + e] = Ma;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// one float4 of a row of pitch ld4 (in float4) per step; the float4s at and beyond C4 are the padding
+__global__ __launch_bounds__(BN_T) void bnp_apply_kernel(const float4 *__restrict__ x, const float *__restrict__ mean, const float *__restrict__ invstd,
+                                                         const float *__restrict__ w, const float *__restrict__ b, float4 *__restrict__ y,
+                                                         int64_t total4, int C4, int ld4, const float4 *__restrict__ residual, int tail) {
+  for (int64_t i = (int64_t)blockIdx.x * BN_T + threadIdx.x; i < total4; i += (int64_t)gridDim.x * BN_T) {
+    const int c4 = (int)(i % ld4);
+    if (c4 >= C4) { y[i] = make_float4(0.f, 0.f, 0.f, 0.f); continue; }
+    const int c = c4 * 4;
+    const float4 v = x[i];
+    const float4 m = *reinterpret_cast<const float4 *>(mean + c), s = *reinterpret_cast<const float4 *>(invstd + c);
+    const float4 ww = *reinterpret_cast<const float4 *>(w + c), bb = *reinterpret_cast<const float4 *>(b + c);
+    float4 o = make_float4(bn_value(v.x, m.x, s.x, ww.x, bb.x), bn_value(v.y, m.y, s.y, ww.y, bb.y), bn_value(v.z, m.z, s.z, ww.z, bb.z),
+                           bn_value(v.w, m.w, s.w, ww.w, bb.w));
+    if (tail == 2) o = relu_nan(o);
+    if (residual) { const float4 r = residual[i]; o.x += r.x; o.y += r.y; o.z += r.z; o.w += r.w; }
+    if (tail == 1) o = relu_nan(o);
+    y[i] = o;
+  }
+}
+
+// the gated incoming gradient of one float4: tail 1 reads the gate off the saved output, tail 2 off bn(x) recomputed, tail 0 has none
+// (a gate value of 1).  Selects: a NaN gate value lets the gradient pass, as torch's threshold_backward does; a closed gate drops a
+// NaN gradient.
+__device__ __forceinline__ float4 bnp_gate(float4 g4, int tail, const float *__restrict__ y, int64_t at, float4 v4, float4 m4, float4 i4,
+                                           const float *__restrict__ w, const float *__restrict__ b, int c) {
+  float t0 = 1.f, t1 = 1.f, t2 = 1.f, t3 = 1.f;
+  if (tail == 1) {
+    const float4 y4 = *reinterpret_cast<const float4 *>(y + at);
+    t0 = y4.x; t1 = y4.y; t2 = y4.z; t3 = y4.w;
+  } else if (tail == 2) {
+    const float4 ww = *reinterpret_cast<const float4 *>(w + c), bb = *reinterpret_cast<const float4 *>(b + c);
+    t0 = bn_value(v4.x, m4.x, i4.x, ww.x, bb.x); t1 = bn_value(v4.y, m4.y, i4.y, ww.y, bb.y);
+    t2 = bn_value(v4.z, m4.z, i4.z, ww.z, bb.z); t3 = bn_value(v4.w, m4.w, i4.w, ww.w, bb.w);
+  }
+  return make_float4(t0 <= 0.f ? 0.f : g4.x, t1 <= 0.f ? 0.f : g4.y, t2 <= 0.f ? 0.f : g4.z, t3 <= 0.f ? 0.f : g4.w);
+}
+
+__global__ __launch_bounds__(BN_T) void bnp_bwd_partial_kernel(const float *__restrict__ x, const float *__restrict__ dy, const float *__restrict__ mean,
+                                                               const float *__restrict__ invstd, const float *__restrict__ w,
+                                                               const float *__restrict__ b, float *__restrict__ ws, int rows, int C, int ld,
+                                                               int rows_per_slab, const float *__restrict__ y_or_null, int tail) {
+  extern __shared__ float bn_lds[];                    // [RL][CG * 4][2]
+  const int C4 = C >> 2;
+  const int CG = C4 < BN_T ? C4 : BN_T, RL = BN_T / CG;
+  const int tid = threadIdx.x, cg = tid % CG, rl = tid / CG;
+  const int r_lo = blockIdx.x * rows_per_slab, r_hi = min(rows, r_lo + rows_per_slab);
+  for (int c0 = 0; c0 < C4; c0 += CG) {
+    const int c4 = c0 + cg;
+    float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
+    if (c4 < C4 && rl < RL) {
+      const float4 m4 = *reinterpret_cast<const float4 *>(mean + c4 * 4), i4 = *reinterpret_cast<const float4 *>(invstd + c4 * 4);
+      const float m[4] = {m4.x, m4.y, m4.z, m4.w}, is[4] = {i4.x, i4.y, i4.z, i4.w};
+      for (int r = r_lo + rl; r < r_hi; r += RL) {
+        const int64_t at = (int64_t)r * ld + c4 * 4;
+        const float4 v4 = *reinterpret_cast<const float4 *>(x + at);
+        const float4 g4 = bnp_gate(*reinterpret_cast<const float4 *>(dy + at), tail, y_or_null, at, v4, m4, i4, w, b, c4 * 4);
+        const float v[4] = {v4.x, v4.y, v4.z, v4.w}, g[4] = {g4.x, g4.y, g4.z, g4.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          s1[e] += g[e];
+          s2[e] += g[e] * ((v[e] - m[e]) * is[e]);
+        }
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        bn_lds[((rl * CG + cg) * 4 + e) * 2 + 0] = s1[e];
+        bn_lds[((rl * CG + cg) * 4 + e) * 2 + 1] = s2[e];
+      }
+    }
+    __syncthreads();
+    if (rl == 0 && c4 < C4) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float a = s1[e], bsum = s2[e];
+        for (int l = 1; l < RL; ++l) {
+          a += bn_lds[((l * CG + cg) * 4 + e) * 2 + 0];
+          bsum += bn_lds[((l * CG + cg) * 4 + e) * 2 + 1];
+        }
+        ws[((int64_t)blockIdx.x * 2 + 0) * C + c4 * 4 + e] = a;
+        ws[((int64_t)blockIdx.x * 2 + 1) * C + c4 * 4 + e] = bsum;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// dres: the gradient of the added identity -- behind the gate for tails 0 / 1 (the add sits in front of the ReLU), the incoming
+// gradient itself for tail 2 (the add sits behind it)
+__global__ __launch_bounds__(BN_T) void bnp_bwd_apply_kernel(const float *__restrict__ x, const float *__restrict__ dy, const float *__restrict__ mean,
+                                                             const float *__restrict__ invstd, const float *__restrict__ w,
+                                                             const float *__restrict__ b, const float *__restrict__ dw,
+                                                             const float *__restrict__ db, float *__restrict__ dx, int64_t total4, int C4, int ld4,
+                                                             float inv_rows, const float *__restrict__ y_or_null, int tail,
+                                                             float *__restrict__ dres_or_null) {
+  for (int64_t i = (int64_t)blockIdx.x * BN_T + threadIdx.x; i < total4; i += (int64_t)gridDim.x * BN_T) {
+    const int c4 = (int)(i % ld4);
+    float4 *dx4 = reinterpret_cast<float4 *>(dx) + i;
+    if (c4 >= C4) {
+      *dx4 = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (dres_or_null) reinterpret_cast<float4 *>(dres_or_null)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      continue;
+    }
+    const int c = c4 * 4;
+    const float4 v4 = reinterpret_cast<const float4 *>(x)[i], raw = reinterpret_cast<const float4 *>(dy)[i];
+    const float4 m4 = *reinterpret_cast<const float4 *>(mean + c), i4 = *reinterpret_cast<const float4 *>(invstd + c);
+    const float4 g4 = bnp_gate(raw, tail, y_or_null, i * 4, v4, m4, i4, w, b, c);
+    if (dres_or_null) {
+      float4 *dres4 = reinterpret_cast<float4 *>(dres_or_null) + i;
+      if (tail == 2) *dres4 = raw; else *dres4 = g4;
+    }
+    const float4 w4 = *reinterpret_cast<const float4 *>(w + c), db4 = *reinterpret_cast<const float4 *>(db + c);
+    const float4 dw4 = *reinterpret_cast<const float4 *>(dw + c);
+    *dx4 = make_float4(bn_dx(v4.x, g4.x, m4.x, i4.x, w4.x, db4.x, dw4.x, inv_rows), bn_dx(v4.y, g4.y, m4.y, i4.y, w4.y, db4.y, dw4.y, inv_rows),
+                       bn_dx(v4.z, g4.z, m4.z, i4.z, w4.z, db4.z, dw4.z, inv_rows), bn_dx(v4.w, g4.w, m4.w, i4.w, w4.w, db4.w, dw4.w, inv_rows));
+  }
+}
+
 static void bn_geometry(int rows, int &G, int &rows_per_slab) {
   G = ceil_div(rows, 64);
   if (G > BN_MAXG) G = BN_MAXG;
@@ -330,4 +520,80 @@ extern "C" int sgc_bn_rows_act_backward(const float *x, const float *dy, const f
                                         float *workspace, int64_t workspace_floats, int rows, int C, sgc_stream_t stream) {
   return bn_backward_impl(x, dy, y_relu_or_null, mean, invstd, weight, dx, dweight, dbias, dresidual_or_null, workspace, workspace_floats, rows, C,
                           stream);
+}
+
+// ---- the padded form: include/sgcdet_amd_depth_train.h ------------------------------------------------------------------------------
+static int bnp_check(const char *who, int rows, int C, int ld, int tail) {
+  if (rows <= 0 || C <= 0) return set_error(SGC_EINVAL, "%s: bad size", who);
+  if (C % 4) return set_error(SGC_EUNSUP, "%s: needs C %% 4 == 0", who);
+  if (ld < C) return set_error(SGC_EUNSUP, "%s: row pitch %d below C = %d", who, ld, C);
+  if (ld % 4) return set_error(SGC_EUNSUP, "%s: needs a row pitch %% 4 == 0 (got %d)", who, ld);
+  if (tail < 0 || tail > 2) return set_error(SGC_EUNSUP, "%s: tail must be 0, 1 or 2", who);
+  return SGC_OK;
+}
+
+extern "C" int sgc_bn_rows_padded_forward(const float *x, const float *weight, const float *bias, float *running_mean_or_null,
+                                          float *running_var_or_null, float momentum, float eps, const float *residual_or_null, int tail,
+                                          float *y, float *mean_out, float *invstd_out, float *workspace, int64_t workspace_floats,
+                                          int rows, int C, int ld, sgc_stream_t stream) {
+  const char *who = "sgc_bn_rows_padded_forward";
+  if (!x || !weight || !bias || !y || !mean_out || !invstd_out || !workspace) return set_error(SGC_EINVAL, "%s: null pointer", who);
+  int rc = bnp_check(who, rows, C, ld, tail);
+  if (rc) return rc;
+  if (tail == 2 && !residual_or_null) return set_error(SGC_EINVAL, "%s: tail 2 (relu, then add) needs a residual", who);
+  if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)residual_or_null | (uintptr_t)weight | (uintptr_t)bias | (uintptr_t)mean_out |
+       (uintptr_t)invstd_out) & 15)
+    return set_error(SGC_EINVAL, "%s: pointers must be 16-byte aligned", who);
+  int G, rps;
+  bn_geometry(rows, G, rps);
+  if (workspace_floats < (int64_t)G * 2 * C) return set_error(SGC_EINVAL, "%s: workspace too small", who);
+  hipStream_t st = (hipStream_t)stream;
+  const int C4 = C / 4, CG = C4 < BN_T ? C4 : BN_T, RL = BN_T / CG;
+  const size_t smem = (size_t)RL * CG * 4 * 3 * sizeof(float);
+  hipLaunchKernelGGL(bnp_stats_partial_kernel, dim3(G), dim3(BN_T), smem, st, x, workspace, rows, C, ld, rps);
+  rc = check_launch("bnp_stats_partial_kernel");
+  if (rc) return rc;
+  hipLaunchKernelGGL(bn_stats_final_kernel, dim3(ceil_div(C, BN_FC)), dim3(BN_T), 0, st, (const float *)workspace, G, rows, rps, C, eps, momentum,
+                     mean_out, invstd_out, running_mean_or_null, running_var_or_null);
+  rc = check_launch("bn_stats_final_kernel");
+  if (rc) return rc;
+  const int64_t total4 = (int64_t)rows * (ld / 4);
+  const int g = (int)((total4 + BN_T - 1) / BN_T < 4096 ? (total4 + BN_T - 1) / BN_T : 4096);
+  hipLaunchKernelGGL(bnp_apply_kernel, dim3(g), dim3(BN_T), 0, st, reinterpret_cast<const float4 *>(x), (const float *)mean_out,
+                     (const float *)invstd_out, weight, bias, reinterpret_cast<float4 *>(y), total4, C4, ld / 4,
+                     reinterpret_cast<const float4 *>(residual_or_null), tail);
+  return check_launch("bnp_apply_kernel");
+}
+
+extern "C" int sgc_bn_rows_padded_backward(const float *x, const float *dy, const float *y_or_null, const float *mean, const float *invstd,
+                                           const float *weight, const float *bias_or_null, float *dx, float *dweight, float *dbias,
+                                           float *dresidual_or_null, int tail, float *workspace, int64_t workspace_floats, int rows, int C,
+                                           int ld, sgc_stream_t stream) {
+  const char *who = "sgc_bn_rows_padded_backward";
+  if (!x || !dy || !mean || !invstd || !weight || !dx || !dweight || !dbias || !workspace) return set_error(SGC_EINVAL, "%s: null pointer", who);
+  int rc = bnp_check(who, rows, C, ld, tail);
+  if (rc) return rc;
+  if (tail == 1 && !y_or_null) return set_error(SGC_EINVAL, "%s: tail 1 reads its gate off the forward's output: y is null", who);
+  if (tail == 2 && !bias_or_null) return set_error(SGC_EINVAL, "%s: tail 2 recomputes its gate from x: bias is null", who);
+  if (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx | (uintptr_t)y_or_null | (uintptr_t)dresidual_or_null | (uintptr_t)mean |
+       (uintptr_t)invstd | (uintptr_t)weight | (uintptr_t)bias_or_null | (uintptr_t)dweight | (uintptr_t)dbias) & 15)
+    return set_error(SGC_EINVAL, "%s: pointers must be 16-byte aligned", who);
+  int G, rps;
+  bn_geometry(rows, G, rps);
+  if (workspace_floats < (int64_t)G * 2 * C) return set_error(SGC_EINVAL, "%s: workspace too small", who);
+  hipStream_t st = (hipStream_t)stream;
+  const int C4 = C / 4, CG = C4 < BN_T ? C4 : BN_T, RL = BN_T / CG;
+  const size_t smem = (size_t)RL * CG * 4 * 2 * sizeof(float);
+  hipLaunchKernelGGL(bnp_bwd_partial_kernel, dim3(G), dim3(BN_T), smem, st, x, dy, mean, invstd, weight, bias_or_null, workspace, rows, C, ld, rps,
+                     y_or_null, tail);
+  rc = check_launch("bnp_bwd_partial_kernel");
+  if (rc) return rc;
+  hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(ceil_div(C, BN_FC)), dim3(BN_T), 0, st, (const float *)workspace, G, C, dweight, dbias);
+  rc = check_launch("bn_bwd_final_kernel");
+  if (rc) return rc;
+  const int64_t total4 = (int64_t)rows * (ld / 4);
+  const int g = (int)((total4 + BN_T - 1) / BN_T < 4096 ? (total4 + BN_T - 1) / BN_T : 4096);
+  hipLaunchKernelGGL(bnp_bwd_apply_kernel, dim3(g), dim3(BN_T), 0, st, x, dy, mean, invstd, weight, bias_or_null, (const float *)dweight,
+                     (const float *)dbias, dx, total4, C4, ld / 4, 1.0f / (float)rows, y_or_null, tail, dresidual_or_null);
+  return check_launch("bnp_bwd_apply_kernel");
 }

@@ -651,6 +651,186 @@ class BatchNormRowsFunction(Function):
         return dx, dw, db, None, None, None, None, dres, None
 
 
+class BatchNormRowsPaddedFunction(Function):
+    """``BatchNormRowsFunction`` for rows whose pitch is wider than the norm: rows [R, ld] of which the first
+    C = ``weight.numel()`` columns are channels and the rest zero padding, the module's own [C] parameters and running statistics,
+    on ``sgc_bn_rows_padded_forward / _backward``.  ``tail`` 0: bn + residual?; 1: relu(bn + residual?); 2: relu(bn) + residual --
+    the U-Net skip, whose gate the backward recomputes from the saved input.  The padding columns of the output and of both
+    gradients are written as zeros whatever the padding of the inputs holds."""
+
+    @staticmethod
+    def forward(ctx, rows, weight, bias, running_mean, running_var, momentum, eps, residual=None, tail=0):
+        x = rows.contiguous()
+        res = None if residual is None else residual.detach().contiguous()
+        w, b = weight.detach().contiguous(), bias.detach().contiguous()
+        y, mean, invstd = ext.ops().bn_rows_padded_forward(x, w, b, running_mean, running_var, momentum, eps, residual=res, tail=tail)
+        ctx.tail, ctx.has_res = int(tail), residual is not None
+        ctx.save_for_backward(x, mean, invstd, w, b, *((y,) if tail == 1 else ()))
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_y):
+        saved = ctx.saved_tensors
+        x, mean, invstd, w, b = saved[:5]
+        want_res = ctx.has_res and ctx.needs_input_grad[7]
+        dx, dw, db, dres = ext.ops().bn_rows_padded_backward(x, grad_y.float().contiguous(), mean, invstd, w, bias=b,
+                                                             y=saved[5] if ctx.tail == 1 else None, tail=ctx.tail, want_dresidual=want_res)
+        return dx, dw, db, None, None, None, None, dres, None
+
+
+def _padded_planes(weight, **form):
+    """The parameter's planes with both channel counts zero-padded to multiples of 32 (the K tile and the rows' pitch)."""
+    return _TRAIN_PLANES.get(weight, pad_rows=32, pad_cols=32, **form)
+
+
+def _pad32(n):
+    return (n + 31) // 32 * 32
+
+
+class PaddedConv2dFunction(Function):
+    """``nn.Conv2d(k, stride, padding=k//2)(x) [+ bias]`` on channels-last rows of PADDED width, for channel counts that are no
+    multiple of 32 (the regulation U-Nets of ``DepthNet_Fusion``: 12 / 24 / 48 and 140 / 280 / 560 channels) --
+    ``FrozenNormConv2dFunction``'s bias form with the parameter at its true shape and the rows at 32-column pitch.
+
+    ``apply(x, weight, bias, nhw, stride)``: x [N*H*W, Cin_p], weight [Cout, Cin, k, k] (the module's parameter), bias [Cout] | None
+    -> y [N*OH*OW, Cout_p], Cin_p / Cout_p = the next multiples of 32.  k = 3 with stride 1 or 2, k = 1 with stride 1.  The padding
+    columns of x must be zeros (or at least finite: they meet zero weight columns); those of y are exactly zero.
+
+    * forward and input gradient: ``conv_plan.conv2d_rows`` on planes packed with zero rows / columns;
+    * weight gradient: ``sgc_conv2d_wgrad_bf16x3`` at the padded sizes, ``sgc_unpack_conv_wgrad`` drops the padding;
+    * bias gradient: ``sgc_rows_colsum`` of dy."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, nhw, stride):
+        from .plugin.conv_plan import conv2d_rows
+        _require_bf16_planes("PaddedConv2dFunction")
+        cout, cin, k = weight.shape[0], weight.shape[1], weight.shape[2]
+        if weight.dim() != 4 or weight.shape[3] != k or (k, stride) not in ((3, 1), (3, 2), (1, 1)):
+            raise RuntimeError("PaddedConv2dFunction: needs a [Cout, Cin, k, k] weight with (k, stride) in (3, 1), (3, 2), (1, 1)")
+        if x.dim() != 2 or x.shape[1] != _pad32(cin) or (bias is not None and bias.shape != (cout,)):
+            raise RuntimeError(f"PaddedConv2dFunction: x must be rows of {_pad32(cin)} columns (Cin = {cin} padded) and bias [Cout]")
+        hi, lo = _padded_planes(weight)                        # [k*k, Cout_p, Cin_p]
+        x = x.float().contiguous()
+        shift = None if bias is None else _pad_cols(bias.detach().float().view(1, -1), 32).view(-1).contiguous()
+        y = conv2d_rows(x, hi, lo, nhw, k, stride, shift=shift, relu=False)
+        ctx.save_for_backward(x, weight)
+        ctx.geom, ctx.has_bias = (tuple(nhw), k, stride), bias is not None
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        from .plugin.conv_plan import conv2d_rows
+        ops = ext.ops()
+        x, weight = ctx.saved_tensors
+        (N, H, W), k, stride = ctx.geom
+        OH, OW = (H + stride - 1) // stride, (W + stride - 1) // stride
+        g = dy.float().contiguous()
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            if stride == 1:
+                hi, lo = _padded_planes(weight, transpose=True, flip=True)           # [k*k, Cin_p, Cout_p], taps mirrored
+                dx = conv2d_rows(g, hi, lo, (N, H, W), k, relu=False)
+            else:
+                hi, lo = _padded_planes(weight, transpose=True)                      # the ConvTranspose2d reading of the parameter
+                up = conv2d_rows(g, hi, lo, (N, OH, OW), 3, stride=2, transposed=True, relu=False)
+                dx = up if (2 * OH, 2 * OW) == (H, W) else up.view(N, 2 * OH, 2 * OW, -1)[:, :H, :W].reshape(N * H * W, -1)
+        if ctx.needs_input_grad[1]:
+            dwk = ops.conv2d_wgrad_bf16x3(x, g, (N, H, W), k, stride)               # [k*k, Cout_p, Cin_p]
+            dw = ops.unpack_conv_wgrad(dwk, weight.shape).to(weight.dtype)
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            db = ops.rows_colsum(g)[:weight.shape[0]].to(weight.dtype)
+        return dx, dw, db, None, None
+
+
+class ConvTranspose2dRowsFunction(Function):
+    """``nn.ConvTranspose2d(3, stride 2, padding 1, output_padding 1, bias=False)`` on channels-last rows of padded width, all three
+    passes on the existing convolution entries.  ``apply(x, weight, nhw)``: x [N*H*W, Cin_p], weight
+    [Cin, Cout, 3, 3] (the module's parameter) -> y [N*2H*2W, Cout_p].
+
+    * forward: the transposed form of ``sgc_conv2d_nhwc_ex_bf16x3`` on the ``transpose=True`` planes [9, Cout_p, Cin_p];
+    * input gradient: dx[n,i,j,ci] = sum dy[n, 2i+kh-1, 2j+kw-1, co] w[ci][co][kh][kw] -- the stride-2 3x3 forward entry on dy with
+      the parameter read as a Conv2d weight [out = Cin][in = Cout], taps not mirrored;
+    * weight gradient: dw[ci][co][kh][kw] = sum x[n,i,j,ci] dy[n, 2i+kh-1, 2j+kw-1, co] -- ``sgc_conv2d_wgrad_bf16x3`` at k = 3,
+      s = 2 with the operands swapped (dy as its x, x as its dy); its [9][Cin_p][Cout_p] result is the parameter's own order."""
+
+    @staticmethod
+    def forward(ctx, x, weight, nhw):
+        from .plugin.conv_plan import conv2d_rows
+        _require_bf16_planes("ConvTranspose2dRowsFunction")
+        if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or x.dim() != 2 or x.shape[1] != _pad32(weight.shape[0]):
+            raise RuntimeError("ConvTranspose2dRowsFunction: needs a [Cin, Cout, 3, 3] weight and rows of Cin padded to 32 columns")
+        hi, lo = _padded_planes(weight, transpose=True)        # [9, Cout_p, Cin_p]
+        x = x.float().contiguous()
+        y = conv2d_rows(x, hi, lo, nhw, 3, stride=2, transposed=True, relu=False)
+        ctx.save_for_backward(x, weight)
+        ctx.nhw = tuple(nhw)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        from .plugin.conv_plan import conv2d_rows
+        ops = ext.ops()
+        x, weight = ctx.saved_tensors
+        N, H, W = ctx.nhw
+        g = dy.float().contiguous()
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            hi, lo = _padded_planes(weight)                    # [9, Cin_p, Cout_p]
+            dx = conv2d_rows(g, hi, lo, (N, 2 * H, 2 * W), 3, stride=2, relu=False)
+        if ctx.needs_input_grad[1]:
+            dwk = ops.conv2d_wgrad_bf16x3(g, x, (N, 2 * H, 2 * W), 3, 2)             # [9, Cin_p, Cout_p]
+            dw = ops.unpack_conv_wgrad(dwk, weight.shape).to(weight.dtype)
+        return dx, dw, None
+
+
+class DepthRegSoftmaxFunction(Function):
+    """``softmax(nn.Conv2d(Cin, D, 3, padding=1)(x) + bias, dim=channels)`` on rows: ``depth_reg`` and the softmax behind it
+    (DESIGN.md 4.14b).  ``apply(x, weight, bias, nhw)``: x [N*H*W, Cin_p], weight [D, Cin, 3, 3], bias [D] -> p [N*H*W, D] dense;
+    D % 4 == 0, D <= 32.
+
+    * forward: ``sgc_conv2d_nhwc_ex_bf16x3`` with shift = bias and the softmax over its D columns in the epilogue (the eval forward);
+    * backward: ``sgc_softmax_rows_backward`` into a 32-column g, then the input gradient (mirrored taps), the weight gradient and
+      ``sgc_rows_colsum`` as in ``FrozenNormConv2dFunction``'s bias form."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, nhw):
+        from .plugin.conv_plan import conv2d_rows
+        _require_bf16_planes("DepthRegSoftmaxFunction")
+        D, cin = weight.shape[0], weight.shape[1]
+        if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or D % 4 or D > 32 or bias is None or bias.shape != (D,):
+            raise RuntimeError("DepthRegSoftmaxFunction: needs a [D, Cin, 3, 3] weight and a [D] bias with D % 4 == 0, D <= 32")
+        if x.dim() != 2 or x.shape[1] != _pad32(cin):
+            raise RuntimeError(f"DepthRegSoftmaxFunction: x must be rows of {_pad32(cin)} columns (Cin = {cin} padded)")
+        hi, lo = _TRAIN_PLANES.get(weight, pad_rows=4, pad_cols=32)                 # [9, D, Cin_p]
+        x = x.float().contiguous()
+        p = conv2d_rows(x, hi, lo, nhw, 3, shift=bias.detach().float().contiguous(), relu=False, softmax_cols=D)
+        ctx.save_for_backward(x, p, weight)
+        ctx.nhw = tuple(nhw)
+        return p
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dp):
+        from .plugin.conv_plan import conv2d_rows
+        ops = ext.ops()
+        x, p, weight = ctx.saved_tensors
+        D = weight.shape[0]
+        g = ops.softmax_rows_backward(p, dp.float().contiguous(), C=D, ldg=32)      # [rows, 32], zero behind D
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            hi, lo = _padded_planes(weight, transpose=True, flip=True)               # [9, Cin_p, 32]
+            dx = conv2d_rows(g, hi, lo, ctx.nhw, 3, relu=False)
+        if ctx.needs_input_grad[1]:
+            dwk = ops.conv2d_wgrad_bf16x3(x, g, ctx.nhw, 3, 1)                       # [9, 32, Cin_p]
+            dw = ops.unpack_conv_wgrad(dwk, weight.shape).to(weight.dtype)
+        if ctx.needs_input_grad[2]:
+            db = ops.rows_colsum(g)[:D].to(weight.dtype)
+        return dx, dw, db, None
+
+
 class LinearRowsFunction(Function):
     """``nn.Linear`` over a row list with all three passes on the MFMA kernels (training path of the view transform:
     value_proj / sampling_offsets / attention_weights / output_proj, TU/deformable_cross_attention.py:417-436,826): forward

@@ -7,7 +7,8 @@ it in ``__call__``.  ``conv2d_rows`` is the one rule that sends a 2-D layer to `
 norm, autograd) and ``BiasConv2d`` (no norm, trainable bias) all reach the entries through it, so the training forward is the eval forward.
 ``TrainConv3d`` is ``ConvSpec``'s training twin (convolution Function + ``bn_rows`` with a live norm and the fused tail): both are built
 by ``make(conv, bn)`` (``conv_spec`` for eval), so the neck walks one plan in either mode; ``TrainConv2d`` and ``TrainStem7`` are the
-same for ``Conv2dSpec`` and ``Stem7Spec`` (the depth net's feature extractors with their live norms).  Eval BatchNorm (running statistics)
+same for ``Conv2dSpec`` and ``Stem7Spec`` (the depth net's feature extractors with their live norms); ``TrainConv2d(pad=True)`` and
+``TrainConvTranspose2d`` are the layers of its regulation U-Nets, on rows zero-padded to 32 columns.  Eval BatchNorm (running statistics)
 and the bias are folded into a per-channel scale / shift for the kernel's epilogue (``fold_norm``, the only copy), weights are
 permuted once to ``[tap][Cout][Cin]``, and channel counts are zero-padded to multiples of 32 (the K tile; ``_pad_to``) with zero
 weight rows, scale 1 and shift 0, so padded output columns are exactly 0.  ``cached_plan`` keeps a module's plan and rebuilds it
@@ -332,24 +333,39 @@ def train_products_ok():
     return CONV_PRODUCTS != 2
 
 
-def bn_rows(bn, rows, grid, residual=None, relu=False, image=False):
+def _count_batch(bn):
+    """Counts this batch in ``num_batches_tracked`` as nn.BatchNorm's forward does and returns the momentum of the running-statistics
+    update (the cumulative average 1 / count when the module's momentum is None)."""
+    momentum = 0.0 if bn.momentum is None else bn.momentum
+    if bn.training and bn.track_running_stats and bn.num_batches_tracked is not None:
+        bn.num_batches_tracked.add_(1)
+        if bn.momentum is None:
+            momentum = 1.0 / float(bn.num_batches_tracked)
+    return momentum
+
+
+def bn_rows(bn, rows, grid, residual=None, relu=False, image=False, channels=None, relu_then_add=False):
     """A BatchNorm3d-like module on channels-last rows [V, C], optionally followed by ``+ residual`` and ``relu`` (the tails of the
     neck's blocks; on the HIP path they run inside the normalisation passes).  ``nn.BatchNorm3d`` over [1, C, X, Y, Z] is the
     statistics of the V rows per channel, i.e. ``F.batch_norm`` on the [V, C] matrix (same running-statistics update); any other
     module (SyncBatchNorm3d, GroupNorm ...) gets the 5-D channels-last view.  ``nn.BatchNorm2d`` over [N, C, H, W] is the same
     statistics of the N * H * W rows (``grid`` = (N, H, W)) and takes the same branch; a 2-D norm of any other type
-    (``SyncBatchNorm`` ...) gets the 4-D NCHW view of the rows."""
+    (``SyncBatchNorm`` ...) gets the 4-D NCHW view of the rows.
+
+    ``channels`` (default None: the rows are as wide as the norm): the rows are zero-padded -- their first ``channels`` columns are
+    the norm's, the rest padding that is never read and comes back as zeros (``BatchNormRowsPaddedFunction``; off the
+    HIP path the same on the slice).  ``relu_then_add`` (with ``relu``): ``relu(bn(rows)) + residual``, the U-Net skip, instead of
+    ``relu(bn(rows) + residual)``; on the HIP path it rides in the padded norm's passes too."""
+    if channels is not None or relu_then_add:
+        return _bn_rows_padded(bn, rows, grid, residual, relu, image, rows.shape[1] if channels is None else channels, relu_then_add)
+
     def tail(y):
         if residual is not None:
             y = y + residual
         return torch.relu(y) if relu else y
     if type(bn) in (torch.nn.BatchNorm3d, torch.nn.BatchNorm2d):
         use_batch = bn.training or (bn.running_mean is None and bn.running_var is None)
-        momentum = 0.0 if bn.momentum is None else bn.momentum
-        if bn.training and bn.track_running_stats and bn.num_batches_tracked is not None:
-            bn.num_batches_tracked.add_(1)
-            if bn.momentum is None:
-                momentum = 1.0 / float(bn.num_batches_tracked)
+        momentum = _count_batch(bn)
         if (use_batch and TRAIN_CONV == "hip" and BN_ON_HIP and rows.is_cuda and rows.dtype == torch.float32 and rows.shape[1] % 4 == 0
                 and bn.weight is not None and bn.bias is not None and rows.shape[0] > 1):
             from ..functions import BatchNormRowsFunction
@@ -369,6 +385,31 @@ def bn_rows(bn, rows, grid, residual=None, relu=False, image=False):
     return tail(y[0].permute(1, 2, 3, 0).reshape(rows.shape[0], rows.shape[1]))
 
 
+def _bn_rows_padded(bn, rows, grid, residual, relu, image, C, relu_then_add):
+    """``bn_rows`` for padded rows and / or the ReLU-then-add tail.  A plain BatchNorm under the conditions of ``bn_rows``' HIP branch
+    takes ``BatchNormRowsPaddedFunction``; everything else is ``bn_rows`` itself on the first ``C`` columns (a view), the tail in torch,
+    zero columns behind.  The bookkeeping of ``num_batches_tracked`` and the momentum is the code above, reached either way."""
+    if relu_then_add and (not relu or residual is None):
+        raise ValueError("bn_rows: relu_then_add is relu(bn) + residual")
+    ld = rows.shape[1]
+    plain = type(bn) in (torch.nn.BatchNorm3d, torch.nn.BatchNorm2d)
+    if (plain and (bn.training or (bn.running_mean is None and bn.running_var is None)) and TRAIN_CONV == "hip" and BN_ON_HIP and BN_FUSE_TAIL
+            and rows.is_cuda and rows.dtype == torch.float32 and C % 4 == 0 and ld % 4 == 0 and bn.weight is not None and bn.bias is not None
+            and rows.shape[0] > 1 and (residual is None or (residual.dtype == torch.float32 and residual.shape == rows.shape))):
+        from ..functions import BatchNormRowsPaddedFunction
+        momentum = _count_batch(bn)
+        track = bn.training and bn.track_running_stats
+        return BatchNormRowsPaddedFunction.apply(rows, bn.weight, bn.bias, bn.running_mean if track else None, bn.running_var if track else None,
+                                                 float(momentum), float(bn.eps), residual, 2 if relu_then_add else int(bool(relu)))
+    res = None if residual is None else residual[:, :C]
+    x = rows[:, :C] if plain else rows[:, :C].contiguous()         # the other norms see an NCHW / NCDHW view of the rows
+    if relu_then_add:
+        y = bn_rows(bn, x, grid, relu=True, image=image) + res
+    else:
+        y = bn_rows(bn, x, grid, residual=res, relu=relu, image=image)
+    return y if ld == C else torch.nn.functional.pad(y, (0, ld - C))
+
+
 class TrainConv2d:
     """To training what ``Conv2dSpec`` is to eval, with its call signature: an ``nn.Conv2d`` (k in {1, 3}, padding k // 2, stride 1
     or 2) with a LIVE norm behind it, under autograd on channels-last rows -- ``TrainConv3d``'s 2-D twin.  Holds the
@@ -377,33 +418,74 @@ class TrainConv2d:
     ``bn_rows`` takes.  ``bn`` None: the convolution and its bias alone (the trunk's final 1x1).  On CPU tensors the convolution is
     torch's, on the NCHW view of the rows; the tails and the norm are the same code."""
 
-    def __init__(self, conv, bn=None):
-        self.conv, self.bn, self.cout = conv, bn, conv.out_channels
+    def __init__(self, conv, bn=None, pad=False):
+        """``pad`` (the regulation U-Nets): rows come and go at the next multiple of 32 columns with zeros behind the
+        channels, for any channel count that is a multiple of 4 -- ``PaddedConv2dFunction`` and the padded norm, which also takes the
+        ReLU-then-add tail into its passes.  Default: the rows are as wide as the layer, as before."""
+        self.conv, self.bn, self.cout, self.pad = conv, bn, conv.out_channels, bool(pad)
 
     def _conv(self, x, nhw):
         conv = self.conv
+        if x.is_cuda and self.pad:
+            from ..functions import PaddedConv2dFunction
+            return PaddedConv2dFunction.apply(x, conv.weight, conv.bias, tuple(nhw), conv.stride[0])
         if x.is_cuda:
             from ..functions import FrozenNormConv2dFunction
             args = (x, conv.weight, None, None, None, tuple(nhw), conv.stride[0], False, False)
             return FrozenNormConv2dFunction.apply(*args) if conv.bias is None else FrozenNormConv2dFunction.apply(*args, conv.bias)
-        y = conv(x.view(nhw[0], nhw[1], nhw[2], x.shape[1]).permute(0, 3, 1, 2))
-        return y.permute(0, 2, 3, 1).reshape(-1, self.cout)
+        y = conv(x.view(nhw[0], nhw[1], nhw[2], x.shape[1])[..., :conv.in_channels].permute(0, 3, 1, 2))
+        y = y.permute(0, 2, 3, 1).reshape(-1, self.cout)
+        return torch.nn.functional.pad(y, (0, _pad_to(self.cout) - self.cout)) if self.pad else y
 
-    def __call__(self, x, nhw, residual=None, relu=True, relu_after_add=False):
+    def __call__(self, x, nhw, residual=None, relu=True, relu_after_add=False, out=None, col0=0):
         """``relu`` / ``relu_after_add`` as ``Conv2dSpec`` has them: relu(bn); relu(bn) + residual; with ``relu_after_add`` (and
-        ``relu`` False) relu(bn + residual)."""
+        ``relu`` False) relu(bn + residual).  ``out`` / ``col0`` are ``Conv2dSpec``'s way of writing into a wider buffer: eval only."""
         s = self.conv.stride[0]
         onhw = (nhw[0], (nhw[1] + s - 1) // s, (nhw[2] + s - 1) // s)
         if relu and relu_after_add:
             raise NotImplementedError("TrainConv2d: relu and relu_after_add exclude each other")
+        if out is not None or col0:
+            raise NotImplementedError("TrainConv2d: a training layer returns its own rows (no `out` buffer)")
         y = self._conv(x, nhw)
         if self.bn is None:
             if residual is not None or relu or relu_after_add:
                 raise NotImplementedError("TrainConv2d: a layer without a norm has no tail")
             return y, onhw
+        if self.pad:
+            return bn_rows(self.bn, y, onhw, residual=residual, relu=bool(relu or relu_after_add), image=True, channels=self.cout,
+                           relu_then_add=bool(relu and residual is not None)), onhw
         if relu and residual is not None:                  # the identity block: the ReLU in the norm's pass, then the skip
             return bn_rows(self.bn, y, onhw, relu=True, image=True) + residual, onhw
         return bn_rows(self.bn, y, onhw, residual=residual, relu=bool(relu or relu_after_add), image=True), onhw
+
+
+class TrainConvTranspose2d:
+    """``TrainConv2d``'s sibling for the up stages of ``SimpleUnet2D``: ``nn.ConvTranspose2d(3, stride 2, padding 1, output_padding 1,
+    bias=False)`` with a LIVE norm behind it on rows of padded width.  Holds the two modules by reference and
+    nothing else.  The convolution is ``ConvTranspose2dRowsFunction`` -- all three passes on the existing entries -- the norm is
+    ``bn_rows`` at padded width, with ``relu(bn) + residual`` (the additive skip) inside its passes.  On CPU tensors the convolution
+    is torch's on the NCHW view of the rows; the norm and the tails are the same code."""
+
+    def __init__(self, conv, bn):
+        if (conv.kernel_size, conv.stride, conv.padding, conv.output_padding) != ((3, 3), (2, 2), (1, 1), (1, 1)) or conv.bias is not None:
+            raise ValueError("TrainConvTranspose2d: ConvTranspose2d(3, stride 2, padding 1, output_padding 1, bias=False)")
+        self.conv, self.bn, self.cout = conv, bn, conv.out_channels
+
+    def __call__(self, x, nhw, residual=None, relu=True, relu_after_add=False, out=None, col0=0):
+        onhw = (nhw[0], 2 * nhw[1], 2 * nhw[2])
+        if relu_after_add or not relu:
+            raise NotImplementedError("TrainConvTranspose2d: relu(bn) [+ residual]")
+        if out is not None or col0:
+            raise NotImplementedError("TrainConvTranspose2d: a training layer returns its own rows (no `out` buffer)")
+        conv = self.conv
+        if x.is_cuda:
+            from ..functions import ConvTranspose2dRowsFunction
+            y = ConvTranspose2dRowsFunction.apply(x, conv.weight, tuple(nhw))
+        else:
+            y = conv(x.view(nhw[0], nhw[1], nhw[2], x.shape[1])[..., :conv.in_channels].permute(0, 3, 1, 2))
+            y = torch.nn.functional.pad(y.permute(0, 2, 3, 1).reshape(-1, self.cout), (0, _pad_to(self.cout) - self.cout))
+        return bn_rows(self.bn, y, onhw, residual=residual, relu=True, image=True, channels=self.cout,
+                       relu_then_add=residual is not None), onhw
 
 
 class TrainStem7:

@@ -25,7 +25,9 @@ half of the module's arithmetic -- run on the same kernels with their BatchNorms
 ``conv_plan.TrainConv2d`` / ``TrainStem7`` layers handed to the one walk ``fnet_mvs_rows``, the stem's weight gradient on
 ``sgc_conv2d_stem7_wgrad_bf16x3``); the three ``SimpleUnet2D``s, ``depth_reg`` and the softmax keep the torch formulation there, and
 ``SGC_DEPTH_NET_TRAIN_HIP=0`` restores it for the extractors (on by default: 45.1 against 51.5 ms forward + backward at config 2,
-profiles/r18_depth_net_train_bench.json).  Eval with autograd and CPU tensors keep the torch formulation (library convolutions)
+profiles/r18_depth_net_train_bench.json).  ``SGC_DEPTH_NET_TRAIN_UNETS=1`` (opt-in) puts the U-Nets, ``depth_reg`` and
+the softmax on the kernels as well (``_regulation_train_hip``: ``_unet`` over ``_unet_train_layers``, rows at 32-column pitch, the live
+norms on ``sgc_bn_rows_padded_*``, ``DepthRegSoftmaxFunction``; 37.6 against 44.8 ms, profiles/r22_depth_unets_train_bench.json).  Eval with autograd and CPU tensors keep the torch formulation (library convolutions)
 throughout.  ``SGC_DEPTH_NET_HIP=0`` restores
 it for the eval forward too (A/B runs); the kernels are the default because the whole-module A/B measured them faster
 (6.9 against 16.4 ms per 40-view scene at config 2, profiles/r10_depth_net_bench.json).  A shape the kernels do not take
@@ -41,7 +43,7 @@ import torch.nn.functional as F
 from .. import ext
 from ..mmcv_lite import HEADS
 from . import conv_plan
-from .conv_plan import Conv2dSpec, TrainConv2d, TrainStem7, cached_plan, image_rows, stem7_spec
+from .conv_plan import Conv2dSpec, TrainConv2d, TrainConvTranspose2d, TrainStem7, cached_plan, image_rows, stem7_spec
 from .plane_sweep import closest_frame_ids, plane_sweep_correlation
 
 
@@ -188,6 +190,7 @@ def homo_warping(src_fea, src_proj, ref_proj, depth_values):
 
 HIP_DEFAULT = "1"      # SGC_DEPTH_NET_HIP when the environment does not set it (DESIGN.md 4.10 says how it was chosen)
 TRAIN_HIP_DEFAULT = "1"      # SGC_DEPTH_NET_TRAIN_HIP likewise: the feature extractors in train mode
+TRAIN_UNETS_DEFAULT = "0"    # SGC_DEPTH_NET_TRAIN_UNETS: the regulation U-Nets, depth_reg and the softmax in train mode too
 
 
 # ---- the eval-mode plan of the 2-D CNNs: folded, padded, permuted layers (``Conv2dSpec``, on the device of the module) ---------
@@ -195,6 +198,14 @@ def _unet_layers(u, in_perm=None, out_perm=None):
     return dict(conv1=Conv2dSpec(u.conv1.conv, u.conv1.bn, in_perm=in_perm), conv2=Conv2dSpec(u.conv2.conv, u.conv2.bn),
                 conv3=Conv2dSpec(u.conv3.conv, u.conv3.bn), conv4=Conv2dSpec(u.conv4.conv, u.conv4.bn),
                 conv9=Conv2dSpec(u.conv9[0], u.conv9[1]), conv11=Conv2dSpec(u.conv11[0], u.conv11[1], out_perm=out_perm))
+
+
+def _unet_train_layers(u):
+    """``_unet_layers``' training twin: the same six keys, the layers live (``TrainConv2d(pad=True)`` / ``TrainConvTranspose2d``: rows
+    at 32-column pitch, the modules held by reference, nothing cached).  ``DepthNet_Fusion._unet`` walks either."""
+    d = {k: TrainConv2d(getattr(u, k).conv, getattr(u, k).bn, pad=True) for k in ("conv1", "conv2", "conv3", "conv4")}
+    d.update(conv9=TrainConvTranspose2d(u.conv9[0], u.conv9[1]), conv11=TrainConvTranspose2d(u.conv11[0], u.conv11[1]))
+    return d
 
 
 def _block_layers(b, make):
@@ -297,8 +308,9 @@ class DepthNet_Fusion(nn.Module):
                 and self.depth_channels <= 32 and xs.dtype == torch.float32 and imgs.dtype == torch.float32)
 
     def _unet(self, x, U, nhw, out=None, col0=0):
-        """SimpleUnet2D on rows: conv0 + conv11(conv2 + conv9(conv4(conv3(conv2(conv1(conv0)))))); the skips ride in the epilogues
-        of the transposed layers, the last of which may write a column range of a wider buffer."""
+        """SimpleUnet2D on rows, eval (``_unet_layers``) and training (``_unet_train_layers``): conv0 + conv11(conv2 +
+        conv9(conv4(conv3(conv2(conv1(conv0)))))); the skips ride in the epilogues of the transposed layers (in training: in the passes of
+        their norms), the last of which may, in eval, write a column range of a wider buffer."""
         c1, n2 = U["conv1"](x, nhw)
         c2, _ = U["conv2"](c1, n2)
         c3, n4 = U["conv3"](c2, n2)
@@ -352,18 +364,56 @@ class DepthNet_Fusion(nn.Module):
         m, _ = TrainConv2d(self.fnet_mono.conv, self.fnet_mono.bn)(rows, (N, H, W))
         return f_mvs, m.view(N, H, W, m.shape[1]).permute(0, 3, 1, 2)
 
+    # ---- train mode on the GPU, opt-in: the U-Nets, depth_reg and the softmax on the kernels as well ----------
+    def _train_unets_ok(self):
+        """With ``_train_hip_ok``: ``SGC_DEPTH_NET_TRAIN_UNETS=1``, every U-Net norm a plain ``nn.BatchNorm2d`` with parameters (a
+        converted SyncBatchNorm keeps the torch formulation for the U-Nets), the norm's HIP passes switched on, and ``depth_reg`` as
+        the reference builds it."""
+        if os.environ.get("SGC_DEPTH_NET_TRAIN_UNETS", TRAIN_UNETS_DEFAULT) != "1":
+            return False
+        if not (conv_plan.TRAIN_CONV == "hip" and conv_plan.BN_ON_HIP and conv_plan.BN_FUSE_TAIL):
+            return False
+        norms = [m for u in (self.correlation_regulation, self.mono_regulation, self.fusion_regulation) for m in u.modules()
+                 if isinstance(m, nn.modules.batchnorm._NormBase)]
+        reg = self.depth_reg
+        return (len(norms) == 18 and all(type(m) is nn.BatchNorm2d and m.weight is not None and m.bias is not None for m in norms)
+                and reg.bias is not None and reg.kernel_size == (3, 3) and reg.stride == (1, 1) and reg.padding == (1, 1))
+
+    def _regulation_train_hip(self, f_mvs, mono, img_meta, stride):
+        """The part of one scene's forward behind the extractors, on rows: cost volume -> ``correlation_regulation``; ``mono`` ->
+        ``mono_regulation``; [cost_reg D | mono_reg 128 | zeros] -> ``fusion_regulation`` -> ``depth_reg`` + softmax.  Returns the
+        probabilities as a logical [N, D, H, W], channels-last-memory view.  The concatenation is the module's channel order (no
+        permutation) as a ``torch.cat`` of rows; the hand-over of the NCHW cost volume is ``NchwToRowsFunction``."""
+        from ..functions import DepthRegSoftmaxFunction, NchwToRowsFunction
+        N, _, H, W = mono.shape
+        D, nhw = self.depth_channels, (N, H, W)
+        corr = self.correlation(f_mvs, img_meta, stride)                                       # [N, D, H, W]
+        corr_rows = F.pad(NchwToRowsFunction.apply(corr).view(N * H * W, D), (0, conv_plan._pad_to(D) - D))
+        cost_reg = self._unet(corr_rows, _unet_train_layers(self.correlation_regulation), nhw)
+        mono_reg = self._unet(mono.permute(0, 2, 3, 1).reshape(N * H * W, -1), _unet_train_layers(self.mono_regulation), nhw)
+        c = D + mono_reg.shape[1]
+        cat = torch.cat([cost_reg[:, :D], mono_reg, mono_reg.new_zeros((N * H * W, conv_plan._pad_to(c) - c))], dim=1)
+        fused = self._unet(cat, _unet_train_layers(self.fusion_regulation), nhw)
+        p = DepthRegSoftmaxFunction.apply(fused, self.depth_reg.weight, self.depth_reg.bias, nhw)
+        return p.view(N, H, W, D).permute(0, 3, 1, 2)
+
     def forward(self, xs, imgs, img_metas, stride):
         """xs [B,N,C,H,W] (finest FPN map), imgs [B,N,3,4H,4W], img_metas list of B dicts -> depth probability
         [B,N,D,H,W] (softmax over the D bins).  Eval mode on the GPU without autograd: ``_forward_hip`` (the result is
         channels-last in memory).  Train mode on the GPU: the feature extractors on the kernels (``_extractors_train_hip``), the
-        U-Nets, ``depth_reg`` and the softmax in the torch formulation below; everything else is that formulation throughout."""
+        U-Nets, ``depth_reg`` and the softmax in the torch formulation below -- or, with ``SGC_DEPTH_NET_TRAIN_UNETS=1``, on the kernels
+        too (``_regulation_train_hip``); everything else is the torch formulation throughout."""
         if (not self.training and not torch.is_grad_enabled() and xs.is_cuda and imgs.is_cuda
                 and os.environ.get("SGC_DEPTH_NET_HIP", HIP_DEFAULT) != "0" and self._hip_ok(xs, imgs)):
             return self._forward_hip(xs, imgs, img_metas, stride)
         train_hip = self._train_hip_ok(xs, imgs)
+        train_unets = train_hip and self._train_unets_ok()
         B, num_src, C, H, W = xs.shape
         depth_preds = torch.empty((B, num_src, self.depth_channels, H, W), device=xs.device)
         for b, (x, img, img_meta) in enumerate(zip(xs, imgs, img_metas)):
+            if train_unets:
+                depth_preds[b] = self._regulation_train_hip(*self._extractors_train_hip(x, img), img_meta, stride)
+                continue
             if train_hip:
                 f_mvs, mono = self._extractors_train_hip(x, img)
                 cost_reg = self.correlation_regulation(self.correlation(f_mvs, img_meta, stride))

@@ -1335,6 +1335,61 @@ class TensorOps:
         self._call("sgc_bn_rows_act_backward", x, dy, y_relu, mean, invstd, weight, dx, dw, db, dres, ws, ws.numel(), rows, Cc)
         return dx, dw, db, dres
 
+    def bn_rows_padded_forward(self, x, weight, bias, running_mean=None, running_var=None, momentum=0.1, eps=1e-5, residual=None, tail=0):
+        """Training-mode BatchNorm over rows x [rows, ld] of which the first C = weight.numel() columns are channels and the rest
+        padding -> (y [rows, ld] with zero padding, mean [C], invstd [C]) (``sgc_bn_rows_padded_forward``,
+        include/sgcdet_amd_depth_train.h).  ``tail`` 0: bn(x) + residual?; 1: relu(bn(x) + residual?); 2: relu(bn(x)) + residual."""
+        self._check(x=x, weight=weight, bias=bias, running_mean=running_mean, running_var=running_var, residual=residual)
+        self._f32(x=x, weight=weight, bias=bias, running_mean=running_mean, running_var=running_var, residual=residual)
+        rows, ld = x.shape
+        Cc = weight.numel()
+        if (bias.numel() != Cc or Cc > ld or (residual is not None and residual.shape != x.shape) or (tail == 2 and residual is None)
+                or any(t is not None and t.numel() != Cc for t in (running_mean, running_var))):
+            raise RuntimeError("bn_rows_padded_forward: inconsistent shapes")
+        y = torch.empty_like(x)
+        mean = torch.empty(Cc, dtype=torch.float32, device=x.device)
+        invstd = torch.empty_like(mean)
+        n = int(self.lib._dll.sgc_bn_rows_workspace_floats(rows, Cc))
+        ws = torch.empty(max(n, 4), dtype=torch.float32, device=x.device)
+        self._call("sgc_bn_rows_padded_forward", x, weight, bias, running_mean, running_var, float(momentum), float(eps), residual, int(tail),
+                   y, mean, invstd, ws, ws.numel(), rows, Cc, ld)
+        return y, mean, invstd
+
+    def bn_rows_padded_backward(self, x, dy, mean, invstd, weight, bias=None, y=None, tail=0, want_dresidual=False):
+        """-> (dx [rows, ld], dweight [C], dbias [C], dresidual [rows, ld] | None) of ``bn_rows_padded_forward``
+        (``sgc_bn_rows_padded_backward``): ``y`` is the forward's output (tail 1 reads its gate there), ``bias`` the norm's (tail 2
+        recomputes its gate from x).  Padding columns of dx and dresidual are zero."""
+        self._check(x=x, dy=dy, mean=mean, invstd=invstd, weight=weight, bias=bias, y=y)
+        self._f32(x=x, dy=dy, mean=mean, invstd=invstd, weight=weight, bias=bias, y=y)
+        rows, ld = x.shape
+        Cc = weight.numel()
+        if (dy.shape != x.shape or mean.numel() != Cc or invstd.numel() != Cc or Cc > ld or (y is not None and y.shape != x.shape)
+                or (bias is not None and bias.numel() != Cc) or (tail == 1 and y is None) or (tail == 2 and bias is None)):
+            raise RuntimeError("bn_rows_padded_backward: inconsistent shapes")
+        dx = torch.empty_like(x)
+        dw = torch.empty(Cc, dtype=torch.float32, device=x.device)
+        db = torch.empty_like(dw)
+        dres = torch.empty_like(x) if want_dresidual else None
+        n = int(self.lib._dll.sgc_bn_rows_workspace_floats(rows, Cc))
+        ws = torch.empty(max(n, 4), dtype=torch.float32, device=x.device)
+        self._call("sgc_bn_rows_padded_backward", x, dy, y if tail == 1 else None, mean, invstd, weight, bias if tail == 2 else None, dx, dw, db,
+                   dres, int(tail), ws, ws.numel(), rows, Cc, ld)
+        return dx, dw, db, dres
+
+    def softmax_rows_backward(self, p, dp, C=None, ldg=None):
+        """g = p * (dp - sum(p * dp)) over the first ``C`` columns of the rows p, dp (default: all of p's) -> g [rows, ldg] with
+        zero columns from C on (``sgc_softmax_rows_backward``); ``ldg`` defaults to C."""
+        self._check(p=p, dp=dp)
+        self._f32(p=p, dp=dp)
+        Cc = p.shape[1] if C is None else int(C)
+        ldg = Cc if ldg is None else int(ldg)
+        if p.dim() != 2 or dp.dim() != 2 or p.shape[0] != dp.shape[0] or p.shape[1] < Cc or dp.shape[1] < Cc or ldg < Cc:
+            raise RuntimeError("softmax_rows_backward: inconsistent shapes")
+        g = torch.empty((p.shape[0], ldg), dtype=torch.float32, device=p.device)
+        if p.shape[0]:
+            self._call("sgc_softmax_rows_backward", p, dp, g, p.shape[0], Cc, p.shape[1], dp.shape[1], ldg)
+        return g
+
     def layer_norm_rows(self, x, gamma, beta, eps=1e-5, count=None, out=None):
         """nn.LayerNorm over the last dim of x [rows, C]; ``count``: int32 device tensor with the live row count."""
         self._check(x=x, gamma=gamma, beta=beta, count=count, out=out)
