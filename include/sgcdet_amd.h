@@ -470,6 +470,9 @@ int sgc_scatter_add_rows(const float *rows, const int64_t *idx, float *vol, int 
  *   scale/shift [Cout] or NULL: folded eval-mode BatchNorm3d (or bias); residual [OV,Cout] or NULL;
  *   ksize in {1,3} (pad = ksize/2), stride in {1,2}, or ksize 2 with stride 2 and no padding (the adjoint geometry of
  *   nn.ConvTranspose3d(2, 2): its input gradient);  y [ox*oy*oz, Cout] fully written.
+ *   Any grid of positive extents, odd ones and axes of extent 1 included (ox = floor((ix + 2 pad - ksize) / stride) + 1); ksize 2
+ *   on an axis of extent 1 leaves no output: SGC_EINVAL.  Any Cout > 0 on a layer that is computed in one pass; a layer that
+ *   sgc_conv3d_workspace_floats (below) reports as split needs Cout % 4 == 0 (SGC_EUNSUP otherwise; callers pad the weight rows).
  * fp32 operands on v_mfma_f32_32x32x2_f32 (exact fp32 products, fp32 accumulation).           */
 int sgc_conv3d_cl_f32(const float *x, const float *wt, const float *scale, const float *shift,
                       const float *residual_or_null, float *y,
@@ -505,7 +508,8 @@ int64_t sgc_conv3d_workspace_floats(int ix, int iy, int iz, int Cin, int Cout, i
  * (TU/transformer.py:151-170) with no NCHW round trip.
  *   x [N*H*W, Cin] -> y [N*H*W, Cout]; w_hi / w_lo [ksize^2][Cout][Cin] (nn.Conv2d weight [Cout,Cin,ky,kx] permuted, split as
  *   for sgc_conv3d_cl_bf16x3); ksize in {1,3} with padding ksize/2, stride 1; scale / shift / residual / relu as above;
- *   Cin % 32 == 0, Cout % 4 == 0.                                                                                       */
+ *   Cin % 32 == 0; any Cout > 0 and any N, H, W > 0 (a width that is no multiple of 4 leaves through element-wise stores; the
+ *   entry carries no workspace and never splits its reduction, so the split rule of the 3-D entries does not apply).        */
 int sgc_conv2d_nhwc_bf16x3(const float *x, const uint16_t *w_hi, const uint16_t *w_lo, const float *scale,
                            const float *shift, const float *residual_or_null, float *y, int N, int H, int W,
                            int Cin, int Cout, int ksize, int relu, sgc_stream_t stream);
@@ -515,7 +519,8 @@ int sgc_conv2d_nhwc_bf16x3(const float *x, const uint16_t *w_hi, const uint16_t 
  *   dw[tap][co][ci] = sum over output voxels o of dy[o][co] * x[nbr(o, tap)][ci]      (bf16x3 arithmetic, fp32 accumulate)
  *   x [ix*iy*iz, Cin], dy [ox*oy*oz, Cout] channels-last rows; dw [ksize^3][Cout][Cin] = nn.Conv3d.weight.grad permuted
  *   like the forward weights.  ksize / stride as above (ksize 2 = the ConvTranspose3d(2,2) layers with x := the fine-grid
- *   tensor, dy := the coarse one); Cin % 4 == 0, Cout % 4 == 0.  The voxel range is split over workgroups; with a
+ *   tensor, dy := the coarse one, and the fine grid of such a layer is even: the kernels of this library refuse ksize 2 on a grid
+ *   with an odd axis, SGC_EUNSUP); Cin % 4 == 0, Cout % 4 == 0.  The voxel range is split over workgroups; with a
  *   workspace of sgc_conv3d_wgrad_workspace_floats(...) floats the partial sums are added in a fixed order (run-to-run
  *   bit-identical); without it one workgroup walks the whole range (slower).  The INPUT gradient needs no entry point of
  *   its own: it is sgc_conv3d_cl_bf16x3 on dy with the taps mirrored and Cin/Cout swapped (stride 1), on the

@@ -1004,6 +1004,7 @@ int sgc_conv3d_cl_f32(const float *x, const float *wt, const float *scale, const
   (void)workspace_or_null; (void)workspace_floats;      /* the oracle never splits a reduction */
   (void)stream;
   if (!x || !wt || !y) return fail(SGC_EINVAL, "null pointer");
+  if (!transposed && ksize == 2 && (ix < 2 || iy < 2 || iz < 2)) return fail(SGC_EINVAL, "ksize 2 on an axis of extent 1 has no output");
   const int pad = ksize == 2 ? 0 : ksize / 2;        /* k2 s2 p0: the adjoint geometry of ConvTranspose3d(2, 2) */
   int ox, oy, oz;
   if (transposed) { ox = 2 * ix; oy = 2 * iy; oz = 2 * iz; }
@@ -1153,6 +1154,7 @@ int sgc_conv3d_wgrad_bf16x3(const float *x, const float *dy, float *dw, int ix, 
                             int ksize, int stride, float *workspace_or_null, int64_t workspace_floats, sgc_stream_t stream) {
   (void)workspace_or_null; (void)workspace_floats; (void)stream;
   if (!x || !dy || !dw) return fail(SGC_EINVAL, "null pointer");
+  if (ksize == 2 && (ix < 2 || iy < 2 || iz < 2)) return fail(SGC_EINVAL, "ksize 2 on an axis of extent 1 has no output");
   const int pad = ksize == 2 ? 0 : ksize / 2;
   const int ox = (ix + 2 * pad - ksize) / stride + 1, oy = (iy + 2 * pad - ksize) / stride + 1, oz = (iz + 2 * pad - ksize) / stride + 1;
   const int taps = ksize * ksize * ksize;

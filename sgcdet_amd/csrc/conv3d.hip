@@ -224,6 +224,8 @@ static int conv_setup(ConvParams &p, const char *who, const float *x, const void
   if (!transposed && !((ksize == 3 || ksize == 1) && (stride == 1 || stride == 2)) && !(ksize == 2 && stride == 2))
     return set_error(SGC_EUNSUP, "%s: ksize in {1,3} with stride in {1,2}, or ksize 2 with stride 2", who);
   if (p.two_d && (transposed || stride != 1)) return set_error(SGC_EUNSUP, "%s: the 2-D form is stride 1, not transposed", who);
+  // ksize 2 has no padding: an axis of extent 1 leaves no output ((1 - 2) / 2 + 1 truncates to 1 in C, floors to 0 in the callers)
+  if (!transposed && ksize == 2 && (ix < 2 || iy < 2 || iz < 2)) return set_error(SGC_EINVAL, "%s: ksize 2 on an axis of extent 1 has no output", who);
   p.x = x; p.y = y; p.relu = relu;
   conv_geometry(p, ix, iy, iz, Cin, Cout, ksize, stride, transposed, ox, oy, oz);
   return SGC_OK;

@@ -977,6 +977,46 @@ def _crop64_case(n, c, hs, ws, h, w):
 CASES += [_crop64_case(2, 64, 9, 12, 7, 8), _crop64_case(2, 64, 5, 8, 5, 4)]
 
 
+def _crop_views_run(ops, t):
+    """The every-2nd- and every-4th-pixel views of the depth pyramid (tests/odd_shape_contract.py), read where they lie: the source
+    stays inside its NaN parent, a pixel read past the view's last row or column would show."""
+    out, seen, orig = {}, [], ops._call
+    ops._call = lambda name, *a, **k: (seen.append(a), orig(name, *a, **k))[1]
+    try:
+        for step, (h, w) in ((2, (7, 10)), (4, (4, 6))):
+            v = t["src"][..., ::step, ::step]
+            out[f"step{step}"] = ops.nchw_to_nhwc_crop(v, h, w)
+            assert seen[-1][0].data_ptr() == v.data_ptr() and seen[-1][8] == step, "the view went through .contiguous()"
+    finally:
+        del ops.__dict__["_call"]
+    return out
+
+
+CASES.append(Case("nchw_to_nhwc_crop-step_2_and_4_views", ("sgc_nchw_to_nhwc_crop",), lambda: dict(src=torch.randn(2, 5, 15, 21, generator=_gen(15 + 21))),
+                  _crop_views_run, tol=0.0,
+                  ref=lambda i: {f"step{s}": i["src"][..., ::s, ::s][..., :h, :w].permute(0, 2, 3, 1).reshape(2, h * w, 5) for s, h, w in ((2, 7, 10), (4, 4, 6))}))
+
+
+# 3 x 3 x 3 stride 2 on an odd grid (tests/odd_shape_contract.py; float64 torch, 1e-4 of the scale): output (4, 3, 2), the last tap of every
+# axis outside the volume.  Cout 28: at 7 the library splits this layer's reduction and a split layer refuses Cout % 4 != 0.
+def _odd_stride2_build():
+    import odd_shape_contract as oc
+    g = _gen(7 + 5 + 3)
+    hi, lo = _oracle().split_bf16(oc.forward_weights(32, (3, 2, False))[1][:, :28].contiguous())
+    return dict(x=oc.forward_input(32, (7, 5, 3)), hi=hi, lo=lo, sc=torch.rand(28, generator=g) + 0.5, sh=torch.randn(28, generator=g),
+                res=torch.randn(24, 28, generator=g))
+
+
+def _odd_stride2_ref(i):
+    import odd_shape_contract as oc
+    return dict(y=oc.apply_epilogue(oc.forward_raw(32, (3, 2, False), (7, 5, 3))[:, :28], i["sc"], i["sh"], i["res"], 1))
+
+
+CASES.append(Case("conv3d_bf16x3-odd_grid_stride_2", ("sgc_conv3d_cl_bf16x3",), _odd_stride2_build,
+                  lambda ops, t: dict(y=ops.conv3d_cl_bf16x3(t["x"], t["hi"], t["lo"], (7, 5, 3), 3, 2, False, t["sc"], t["sh"], t["res"], 1)[0]),
+                  ref=_odd_stride2_ref, tol=1e-4))
+
+
 # ======================================================================================================================================
 # heads and post-processing (tests/test_gpu_kernels.py; kept indices, targets and masks are exact against the oracle)
 # ======================================================================================================================================
