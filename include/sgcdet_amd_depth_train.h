@@ -29,7 +29,7 @@ extern "C" {
  *   the ReLU keeps a NaN (v < 0 ? 0 : v);
  *   workspace >= sgc_bn_rows_workspace_floats(rows, C) floats (the dense query: the partial statistics are [C] wide).
  * Statistics and the running-statistics update are those of sgc_bn_rows_forward (fixed-order Welford / Chan merge, unbiased
- * running variance): for ld == C and tails 0 / 1 every output is bit-identical to sgc_bn_rows_act_forward's (relu = tail).
+ * running variance): sgc_bn_rows_act_forward is the same kernels at ld == C (relu = tail 0 / 1), and the pitch changes no bit.
  * C % 4 == 0, ld % 4 == 0, ld >= C, tail in {0, 1, 2} (SGC_EUNSUP otherwise); 16-byte aligned row matrices, weight, bias, mean_out,
  * invstd_out; rows >= 1 (SGC_EINVAL otherwise). */
 int sgc_bn_rows_padded_forward(const float *x, const float *weight, const float *bias, float *running_mean_or_null,
@@ -46,7 +46,7 @@ int sgc_bn_rows_padded_forward(const float *x, const float *weight, const float 
  * The gate is a select on `value <= 0`: a NaN gate value lets dy pass, a closed gate drops a NaN of dy.
  *   x, dy, y, dx, dresidual [rows, ld]; columns [C, ld) of x, dy, y are never read, those of dx and dresidual are written as +0.0;
  *   y_or_null: required for tail 1, ignored otherwise;  bias_or_null: required for tail 2, ignored otherwise.
- * For ld == C and tails 0 / 1 every output is bit-identical to sgc_bn_rows_act_backward's (y_relu = tail 1's y).
+ * sgc_bn_rows_act_backward is the same kernels at ld == C (y_relu = tail 1's y; without it, tail 0).
  * Refusals as the forward's; mean, invstd, weight, bias, dweight, dbias 16-byte aligned too. */
 int sgc_bn_rows_padded_backward(const float *x, const float *dy, const float *y_or_null, const float *mean, const float *invstd,
                                 const float *weight, const float *bias_or_null, float *dx, float *dweight, float *dbias,

@@ -420,6 +420,45 @@ class ChannelsLastConv3dFunction(Function):
         return dx, dw, None, None, None
 
 
+def _conv2d_rows(*args, **kwargs):
+    """``conv_plan.conv2d_rows``, the one dispatch rule of the 2-D entries (imported at the call: conv_plan imports this module)."""
+    from .plugin.conv_plan import conv2d_rows
+    return conv2d_rows(*args, **kwargs)
+
+
+def _conv2d_input_grad(g, weight, nhw, k, stride, planes):
+    """dx [N*H*W, Cin] of ``nn.Conv2d(k, stride, padding=k//2)`` over nhw = (N, H, W) from g = dL/dy [N*OH*OW, Cout] rows, on the
+    forward entries.  ``planes``: ``_TRAIN_PLANES.get`` or ``_padded_planes`` (then both widths are the padded ones).  Stride 1 -- the
+    forward entry on g with the taps mirrored and Cin / Cout swapped; 3x3 stride 2 -- the transposed form of
+    ``sgc_conv2d_nhwc_ex_bf16x3`` (sums by output parity, 2.25 taps per pixel), cropped to H x W when a side is odd; 1x1 stride 2
+    -- the 1x1 GEMM on g, written to the even positions of a zeroed map."""
+    N, H, W = nhw
+    OH, OW = (H + stride - 1) // stride, (W + stride - 1) // stride
+    if stride == 1:
+        hi, lo = planes(weight, transpose=True, flip=True)         # [k*k, Cin, Cout], taps mirrored
+        return _conv2d_rows(g, hi, lo, (N, H, W), k, relu=False)
+    hi, lo = planes(weight, transpose=True)                        # the ConvTranspose2d reading of the parameter
+    if k == 3:
+        up = _conv2d_rows(g, hi, lo, (N, OH, OW), 3, stride=2, transposed=True, relu=False)      # [N * 2 OH * 2 OW, Cin]
+        return up if (2 * OH, 2 * OW) == (H, W) else up.view(N, 2 * OH, 2 * OW, -1)[:, :H, :W].reshape(N * H * W, -1)
+    t = _conv2d_rows(g, hi, lo, (N, OH, OW), 1, relu=False)
+    dx = torch.zeros((N, H, W, t.shape[1]), dtype=torch.float32, device=g.device)
+    dx[:, ::2, ::2] = t.view(N, OH, OW, -1)
+    return dx.view(N * H * W, -1)
+
+
+def _conv2d_weight_grad(x, g, weight, nhw, k, stride):
+    """dL/dweight in the parameter's shape and dtype: ``sgc_conv2d_wgrad_bf16x3`` ([k*k, Cout, Cin] at the rows' widths), then
+    ``sgc_unpack_conv_wgrad``, which drops any padding."""
+    ops = ext.ops()
+    return ops.unpack_conv_wgrad(ops.conv2d_wgrad_bf16x3(x, g, tuple(nhw), k, stride), weight.shape).to(weight.dtype)
+
+
+def _conv2d_bias_grad(g, weight):
+    """The column sums of g (``sgc_rows_colsum``) over the parameter's Cout columns."""
+    return ext.ops().rows_colsum(g)[:weight.shape[0]].to(weight.dtype)
+
+
 class FrozenNormConv2dFunction(Function):
     """``act(norm(nn.Conv2d(k, stride, padding=k//2, bias=False)(x)) [+ residual])`` with a FROZEN norm (eval statistics, no
     gradient to its parameters: the ResNet backbone in every reference config) on channels-last rows, all three passes on the
@@ -447,7 +486,6 @@ class FrozenNormConv2dFunction(Function):
 
     @staticmethod
     def forward(ctx, x, weight, scale, shift, residual, nhw, stride, relu, relu_after_add, bias=None):
-        from .plugin.conv_plan import conv2d_rows
         _require_bf16_planes("FrozenNormConv2dFunction")
         cout, cin, k = weight.shape[0], weight.shape[1], weight.shape[2]
         if weight.dim() != 4 or weight.shape[3] != k or k not in (1, 3) or stride not in (1, 2) or cin % 32 or cout % 32:
@@ -466,7 +504,7 @@ class FrozenNormConv2dFunction(Function):
         res = None if residual is None else residual.detach().float().contiguous()
         scale = None if scale is None else scale.detach().float().contiguous()
         shift = None if shift is None else shift.detach().float().contiguous()
-        y = conv2d_rows(x, hi, lo, nhw, k, stride, scale=scale, shift=shift, residual=res, relu=relu, relu_after_add=relu_after_add)
+        y = _conv2d_rows(x, hi, lo, nhw, k, stride, scale=scale, shift=shift, residual=res, relu=relu, relu_after_add=relu_after_add)
         ctx.save_for_backward(x, y, weight, scale)
         ctx.geom = (tuple(nhw), k, stride, bool(relu or relu_after_add), residual is not None)
         ctx.has_bias = bias is not None
@@ -478,8 +516,6 @@ class FrozenNormConv2dFunction(Function):
         ops = ext.ops()
         x, y, weight, scale = ctx.saved_tensors
         (N, H, W), k, stride, gated, has_res = ctx.geom
-        OH, OW = (H + stride - 1) // stride, (W + stride - 1) // stride
-        cin = weight.shape[1]
         dy = dy.float().contiguous()
         want_res = has_res and ctx.needs_input_grad[4]
         if gated or scale is not None:
@@ -488,28 +524,11 @@ class FrozenNormConv2dFunction(Function):
                 gres = dy
         else:
             g, gres = dy, (dy if want_res else None)
-        dx = dw = None
-        if ctx.needs_input_grad[0]:
-            from .plugin.conv_plan import conv2d_rows
-            if stride == 1:
-                hi, lo = _TRAIN_PLANES.get(weight, transpose=True, flip=True)        # [k*k, Cin, Cout], taps mirrored
-                dx = conv2d_rows(g, hi, lo, (N, H, W), k, relu=False)
-            elif k == 3:
-                hi, lo = _TRAIN_PLANES.get(weight, transpose=True)                   # the ConvTranspose2d reading of the parameter
-                up = conv2d_rows(g, hi, lo, (N, OH, OW), 3, stride=2, transposed=True, relu=False)       # [N * 2 OH * 2 OW, Cin]
-                dx = up if (2 * OH, 2 * OW) == (H, W) else up.view(N, 2 * OH, 2 * OW, cin)[:, :H, :W].reshape(N * H * W, cin)
-            else:
-                hi, lo = _TRAIN_PLANES.get(weight, transpose=True)
-                t = conv2d_rows(g, hi, lo, (N, OH, OW), 1, relu=False)
-                dx = torch.zeros((N, H, W, cin), dtype=torch.float32, device=g.device)
-                dx[:, ::2, ::2] = t.view(N, OH, OW, cin)
-                dx = dx.view(N * H * W, cin)
-        if ctx.needs_input_grad[1]:
-            dwk = ops.conv2d_wgrad_bf16x3(x, g, (N, H, W), k, stride)               # [k*k, Cout, Cin]
-            dw = ops.unpack_conv_wgrad(dwk, weight.shape).to(weight.dtype)
+        dx = _conv2d_input_grad(g, weight, (N, H, W), k, stride, _TRAIN_PLANES.get) if ctx.needs_input_grad[0] else None
+        dw = _conv2d_weight_grad(x, g, weight, (N, H, W), k, stride) if ctx.needs_input_grad[1] else None
         if not ctx.has_bias:
             return dx, dw, None, None, gres, None, None, None, None
-        db = ops.rows_colsum(g).to(weight.dtype) if ctx.needs_input_grad[9] else None       # g is dy: no gate, no scale
+        db = _conv2d_bias_grad(g, weight) if ctx.needs_input_grad[9] else None       # g is dy: no gate, no scale
         return dx, dw, None, None, gres, None, None, None, None, db
 
 
@@ -612,71 +631,55 @@ class ChannelsLastConvTranspose3dFunction(Function):
 
 class BatchNormRowsFunction(Function):
     """Training-mode ``nn.BatchNorm3d`` on channels-last rows [rows, C] (necks/imvoxelnet.py:36-64: every convolution of the neck
-    is followed by one): statistics, normalisation and the backward reductions on ``sgc_bn_rows_forward / _backward`` (ordered
+    is followed by one): statistics, normalisation and the backward reductions on the ``sgc_bn_rows_*`` kernels (ordered
     reductions: the same bits every run) instead of torch's channels-last batch-norm kernels.  The running statistics are
     updated in place by the forward kernel, as ``F.batch_norm(training=True)`` does.
 
-    ``residual`` / ``relu`` (round 5): the elementwise tail of the neck's blocks inside the same passes -- ``relu(norm(conv))`` and the
-    ResBlock tail ``relu(norm2(conv2) + identity)`` -- i.e. ``y = relu(bn(rows) + residual)`` forward, and backward the incoming
-    gradient masked where ``y > 0`` (torch's ``threshold_backward``) before the BatchNorm backward; the identity's gradient is that
-    masked gradient (``sgc_bn_rows_act_forward / _backward``)."""
+    ``residual`` / ``tail`` (round 5): the elementwise tail of a block inside the same passes.  ``tail`` 0 (False): bn + residual?;
+    1 (True): relu(bn + residual?) -- ``relu(norm(conv))`` and the ResBlock tail ``relu(norm2(conv2) + identity)``, backward the
+    incoming gradient masked where ``y > 0`` (torch's ``threshold_backward``) before the BatchNorm backward, the identity's gradient
+    being that masked gradient; 2: relu(bn) + residual -- the U-Net skip, whose gate the backward recomputes from the saved input.
+
+    ``channels`` None: the rows are as wide as the norm and ``tail`` is 0 or 1 (``sgc_bn_rows_forward / _backward`` and their
+    ``_act_`` forms).  ``channels`` given: rows [R, ld] of which the first C = ``weight.numel()`` columns are
+    channels and the rest zero padding, the module's own [C] parameters and running statistics, on ``sgc_bn_rows_padded_forward /
+    _backward``; the padding columns of the output and of both gradients are written as zeros whatever the padding of the inputs
+    holds.  Both are the same kernels, so the choice decides the entry point and nothing about the values."""
 
     @staticmethod
-    def forward(ctx, rows, weight, bias, running_mean, running_var, momentum, eps, residual=None, relu=False):
+    def forward(ctx, rows, weight, bias, running_mean, running_var, momentum, eps, residual=None, tail=0, channels=None):
         ops = ext.ops()
-        x = rows.contiguous()
-        res = None if residual is None else residual.detach().contiguous()
-        y, mean, invstd = ops.bn_rows_forward(x, weight.detach().contiguous(), bias.detach().contiguous(), running_mean, running_var,
-                                              momentum, eps, residual=res, relu=relu)
-        ctx.relu, ctx.has_res = bool(relu), residual is not None
-        if relu:
-            ctx.save_for_backward(x, mean, invstd, weight.detach(), y)
-        else:
-            ctx.save_for_backward(x, mean, invstd, weight.detach())
-        return y
-
-    @staticmethod
-    def backward(ctx, grad_y):
-        saved = ctx.saved_tensors
-        x, mean, invstd, weight = saved[:4]
-        g = grad_y.contiguous()
-        if not ctx.relu and not ctx.has_res:
-            dx, dw, db = ext.ops().bn_rows_backward(x, g, mean, invstd, weight.contiguous())
-            return dx, dw, db, None, None, None, None, None, None
-        want_res = ctx.has_res and ctx.needs_input_grad[7]
-        if not ctx.relu:                               # no mask: the identity's gradient IS the incoming gradient
-            dx, dw, db = ext.ops().bn_rows_backward(x, g, mean, invstd, weight.contiguous())
-            return dx, dw, db, None, None, None, None, (g if want_res else None), None
-        dx, dw, db, dres = ext.ops().bn_rows_backward(x, g, mean, invstd, weight.contiguous(), y_relu=saved[4], want_dresidual=want_res)
-        return dx, dw, db, None, None, None, None, dres, None
-
-
-class BatchNormRowsPaddedFunction(Function):
-    """``BatchNormRowsFunction`` for rows whose pitch is wider than the norm: rows [R, ld] of which the first
-    C = ``weight.numel()`` columns are channels and the rest zero padding, the module's own [C] parameters and running statistics,
-    on ``sgc_bn_rows_padded_forward / _backward``.  ``tail`` 0: bn + residual?; 1: relu(bn + residual?); 2: relu(bn) + residual --
-    the U-Net skip, whose gate the backward recomputes from the saved input.  The padding columns of the output and of both
-    gradients are written as zeros whatever the padding of the inputs holds."""
-
-    @staticmethod
-    def forward(ctx, rows, weight, bias, running_mean, running_var, momentum, eps, residual=None, tail=0):
+        tail = int(tail)
+        if channels is None and tail == 2:
+            raise ValueError("BatchNormRowsFunction: tail 2 is a padded-entry tail (pass channels)")
         x = rows.contiguous()
         res = None if residual is None else residual.detach().contiguous()
         w, b = weight.detach().contiguous(), bias.detach().contiguous()
-        y, mean, invstd = ext.ops().bn_rows_padded_forward(x, w, b, running_mean, running_var, momentum, eps, residual=res, tail=tail)
-        ctx.tail, ctx.has_res = int(tail), residual is not None
+        if channels is None:
+            y, mean, invstd = ops.bn_rows_forward(x, w, b, running_mean, running_var, momentum, eps, residual=res, relu=bool(tail))
+        else:
+            y, mean, invstd = ops.bn_rows_padded_forward(x, w, b, running_mean, running_var, momentum, eps, residual=res, tail=tail)
+        ctx.tail, ctx.has_res, ctx.padded = tail, residual is not None, channels is not None
         ctx.save_for_backward(x, mean, invstd, w, b, *((y,) if tail == 1 else ()))
         return y
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_y):
+        ops = ext.ops()
         saved = ctx.saved_tensors
         x, mean, invstd, w, b = saved[:5]
+        g = grad_y.float().contiguous()
         want_res = ctx.has_res and ctx.needs_input_grad[7]
-        dx, dw, db, dres = ext.ops().bn_rows_padded_backward(x, grad_y.float().contiguous(), mean, invstd, w, bias=b,
-                                                             y=saved[5] if ctx.tail == 1 else None, tail=ctx.tail, want_dresidual=want_res)
-        return dx, dw, db, None, None, None, None, dres, None
+        if ctx.padded:
+            dx, dw, db, dres = ops.bn_rows_padded_backward(x, g, mean, invstd, w, bias=b, y=saved[5] if ctx.tail == 1 else None,
+                                                           tail=ctx.tail, want_dresidual=want_res)
+        elif ctx.tail:
+            dx, dw, db, dres = ops.bn_rows_backward(x, g, mean, invstd, w, y_relu=saved[5], want_dresidual=want_res)
+        else:                                          # no mask: the identity's gradient IS the incoming gradient
+            dx, dw, db = ops.bn_rows_backward(x, g, mean, invstd, w)
+            dres = g if want_res else None
+        return dx, dw, db, None, None, None, None, dres, None, None
 
 
 def _padded_planes(weight, **form):
@@ -703,7 +706,6 @@ class PaddedConv2dFunction(Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, nhw, stride):
-        from .plugin.conv_plan import conv2d_rows
         _require_bf16_planes("PaddedConv2dFunction")
         cout, cin, k = weight.shape[0], weight.shape[1], weight.shape[2]
         if weight.dim() != 4 or weight.shape[3] != k or (k, stride) not in ((3, 1), (3, 2), (1, 1)):
@@ -713,7 +715,7 @@ class PaddedConv2dFunction(Function):
         hi, lo = _padded_planes(weight)                        # [k*k, Cout_p, Cin_p]
         x = x.float().contiguous()
         shift = None if bias is None else _pad_cols(bias.detach().float().view(1, -1), 32).view(-1).contiguous()
-        y = conv2d_rows(x, hi, lo, nhw, k, stride, shift=shift, relu=False)
+        y = _conv2d_rows(x, hi, lo, nhw, k, stride, shift=shift, relu=False)
         ctx.save_for_backward(x, weight)
         ctx.geom, ctx.has_bias = (tuple(nhw), k, stride), bias is not None
         return y
@@ -721,26 +723,12 @@ class PaddedConv2dFunction(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, dy):
-        from .plugin.conv_plan import conv2d_rows
-        ops = ext.ops()
         x, weight = ctx.saved_tensors
-        (N, H, W), k, stride = ctx.geom
-        OH, OW = (H + stride - 1) // stride, (W + stride - 1) // stride
+        nhw, k, stride = ctx.geom
         g = dy.float().contiguous()
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            if stride == 1:
-                hi, lo = _padded_planes(weight, transpose=True, flip=True)           # [k*k, Cin_p, Cout_p], taps mirrored
-                dx = conv2d_rows(g, hi, lo, (N, H, W), k, relu=False)
-            else:
-                hi, lo = _padded_planes(weight, transpose=True)                      # the ConvTranspose2d reading of the parameter
-                up = conv2d_rows(g, hi, lo, (N, OH, OW), 3, stride=2, transposed=True, relu=False)
-                dx = up if (2 * OH, 2 * OW) == (H, W) else up.view(N, 2 * OH, 2 * OW, -1)[:, :H, :W].reshape(N * H * W, -1)
-        if ctx.needs_input_grad[1]:
-            dwk = ops.conv2d_wgrad_bf16x3(x, g, (N, H, W), k, stride)               # [k*k, Cout_p, Cin_p]
-            dw = ops.unpack_conv_wgrad(dwk, weight.shape).to(weight.dtype)
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            db = ops.rows_colsum(g)[:weight.shape[0]].to(weight.dtype)
+        dx = _conv2d_input_grad(g, weight, nhw, k, stride, _padded_planes) if ctx.needs_input_grad[0] else None
+        dw = _conv2d_weight_grad(x, g, weight, nhw, k, stride) if ctx.needs_input_grad[1] else None       # at the padded sizes
+        db = _conv2d_bias_grad(g, weight) if ctx.has_bias and ctx.needs_input_grad[2] else None
         return dx, dw, db, None, None
 
 
@@ -757,13 +745,12 @@ class ConvTranspose2dRowsFunction(Function):
 
     @staticmethod
     def forward(ctx, x, weight, nhw):
-        from .plugin.conv_plan import conv2d_rows
         _require_bf16_planes("ConvTranspose2dRowsFunction")
         if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or x.dim() != 2 or x.shape[1] != _pad32(weight.shape[0]):
             raise RuntimeError("ConvTranspose2dRowsFunction: needs a [Cin, Cout, 3, 3] weight and rows of Cin padded to 32 columns")
         hi, lo = _padded_planes(weight, transpose=True)        # [9, Cout_p, Cin_p]
         x = x.float().contiguous()
-        y = conv2d_rows(x, hi, lo, nhw, 3, stride=2, transposed=True, relu=False)
+        y = _conv2d_rows(x, hi, lo, nhw, 3, stride=2, transposed=True, relu=False)
         ctx.save_for_backward(x, weight)
         ctx.nhw = tuple(nhw)
         return y
@@ -771,18 +758,14 @@ class ConvTranspose2dRowsFunction(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, dy):
-        from .plugin.conv_plan import conv2d_rows
-        ops = ext.ops()
         x, weight = ctx.saved_tensors
         N, H, W = ctx.nhw
         g = dy.float().contiguous()
-        dx = dw = None
+        dx = None
         if ctx.needs_input_grad[0]:
             hi, lo = _padded_planes(weight)                    # [9, Cin_p, Cout_p]
-            dx = conv2d_rows(g, hi, lo, (N, 2 * H, 2 * W), 3, stride=2, relu=False)
-        if ctx.needs_input_grad[1]:
-            dwk = ops.conv2d_wgrad_bf16x3(g, x, (N, 2 * H, 2 * W), 3, 2)             # [9, Cin_p, Cout_p]
-            dw = ops.unpack_conv_wgrad(dwk, weight.shape).to(weight.dtype)
+            dx = _conv2d_rows(g, hi, lo, (N, 2 * H, 2 * W), 3, stride=2, relu=False)
+        dw = _conv2d_weight_grad(g, x, weight, (N, 2 * H, 2 * W), 3, 2) if ctx.needs_input_grad[1] else None      # operands swapped
         return dx, dw, None
 
 
@@ -797,7 +780,6 @@ class DepthRegSoftmaxFunction(Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, nhw):
-        from .plugin.conv_plan import conv2d_rows
         _require_bf16_planes("DepthRegSoftmaxFunction")
         D, cin = weight.shape[0], weight.shape[1]
         if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or D % 4 or D > 32 or bias is None or bias.shape != (D,):
@@ -806,7 +788,7 @@ class DepthRegSoftmaxFunction(Function):
             raise RuntimeError(f"DepthRegSoftmaxFunction: x must be rows of {_pad32(cin)} columns (Cin = {cin} padded)")
         hi, lo = _TRAIN_PLANES.get(weight, pad_rows=4, pad_cols=32)                 # [9, D, Cin_p]
         x = x.float().contiguous()
-        p = conv2d_rows(x, hi, lo, nhw, 3, shift=bias.detach().float().contiguous(), relu=False, softmax_cols=D)
+        p = _conv2d_rows(x, hi, lo, nhw, 3, shift=bias.detach().float().contiguous(), relu=False, softmax_cols=D)
         ctx.save_for_backward(x, p, weight)
         ctx.nhw = tuple(nhw)
         return p
@@ -814,20 +796,11 @@ class DepthRegSoftmaxFunction(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, dp):
-        from .plugin.conv_plan import conv2d_rows
-        ops = ext.ops()
         x, p, weight = ctx.saved_tensors
-        D = weight.shape[0]
-        g = ops.softmax_rows_backward(p, dp.float().contiguous(), C=D, ldg=32)      # [rows, 32], zero behind D
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            hi, lo = _padded_planes(weight, transpose=True, flip=True)               # [9, Cin_p, 32]
-            dx = conv2d_rows(g, hi, lo, ctx.nhw, 3, relu=False)
-        if ctx.needs_input_grad[1]:
-            dwk = ops.conv2d_wgrad_bf16x3(x, g, ctx.nhw, 3, 1)                       # [9, 32, Cin_p]
-            dw = ops.unpack_conv_wgrad(dwk, weight.shape).to(weight.dtype)
-        if ctx.needs_input_grad[2]:
-            db = ops.rows_colsum(g)[:D].to(weight.dtype)
+        g = ext.ops().softmax_rows_backward(p, dp.float().contiguous(), C=weight.shape[0], ldg=32)      # [rows, 32], zero behind D
+        dx = _conv2d_input_grad(g, weight, ctx.nhw, 3, 1, _padded_planes) if ctx.needs_input_grad[0] else None     # planes [9, Cin_p, 32]
+        dw = _conv2d_weight_grad(x, g, weight, ctx.nhw, 3, 1) if ctx.needs_input_grad[1] else None                # from [9, 32, Cin_p]
+        db = _conv2d_bias_grad(g, weight) if ctx.needs_input_grad[2] else None
         return dx, dw, db, None
 
 

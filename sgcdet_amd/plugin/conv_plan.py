@@ -344,6 +344,26 @@ def _count_batch(bn):
     return momentum
 
 
+def _bn_on_kernels(bn, rows, C):
+    """May this norm over the first ``C`` columns of ``rows`` run on ``sgc_bn_rows_*``?  A plain BatchNorm2d / 3d with affine
+    parameters that normalises with batch statistics, on the HIP training path, over more than one CUDA fp32 row, norm and rows of a
+    width the 16-byte loads accept."""
+    return (type(bn) in (torch.nn.BatchNorm3d, torch.nn.BatchNorm2d) and (bn.training or (bn.running_mean is None and bn.running_var is None))
+            and TRAIN_CONV == "hip" and BN_ON_HIP and rows.is_cuda and rows.dtype == torch.float32 and C % 4 == 0 and rows.shape[1] % 4 == 0
+            and bn.weight is not None and bn.bias is not None and rows.shape[0] > 1)
+
+
+def _residual_fits(residual, rows):
+    return residual is None or (residual.dtype == torch.float32 and residual.shape == rows.shape)
+
+
+def _bn_function(bn, rows, momentum, residual, tail, channels=None):
+    from ..functions import BatchNormRowsFunction
+    track = bn.training and bn.track_running_stats
+    return BatchNormRowsFunction.apply(rows, bn.weight, bn.bias, bn.running_mean if track else None, bn.running_var if track else None,
+                                       float(momentum), float(bn.eps), residual, tail, channels)
+
+
 def bn_rows(bn, rows, grid, residual=None, relu=False, image=False, channels=None, relu_then_add=False):
     """A BatchNorm3d-like module on channels-last rows [V, C], optionally followed by ``+ residual`` and ``relu`` (the tails of the
     neck's blocks; on the HIP path they run inside the normalisation passes).  ``nn.BatchNorm3d`` over [1, C, X, Y, Z] is the
@@ -353,7 +373,7 @@ def bn_rows(bn, rows, grid, residual=None, relu=False, image=False, channels=Non
     (``SyncBatchNorm`` ...) gets the 4-D NCHW view of the rows.
 
     ``channels`` (default None: the rows are as wide as the norm): the rows are zero-padded -- their first ``channels`` columns are
-    the norm's, the rest padding that is never read and comes back as zeros (``BatchNormRowsPaddedFunction``; off the
+    the norm's, the rest padding that is never read and comes back as zeros (``BatchNormRowsFunction`` with ``channels``; off the
     HIP path the same on the slice).  ``relu_then_add`` (with ``relu``): ``relu(bn(rows)) + residual``, the U-Net skip, instead of
     ``relu(bn(rows) + residual)``; on the HIP path it rides in the padded norm's passes too."""
     if channels is not None or relu_then_add:
@@ -366,14 +386,9 @@ def bn_rows(bn, rows, grid, residual=None, relu=False, image=False, channels=Non
     if type(bn) in (torch.nn.BatchNorm3d, torch.nn.BatchNorm2d):
         use_batch = bn.training or (bn.running_mean is None and bn.running_var is None)
         momentum = _count_batch(bn)
-        if (use_batch and TRAIN_CONV == "hip" and BN_ON_HIP and rows.is_cuda and rows.dtype == torch.float32 and rows.shape[1] % 4 == 0
-                and bn.weight is not None and bn.bias is not None and rows.shape[0] > 1):
-            from ..functions import BatchNormRowsFunction
-            track = bn.training and bn.track_running_stats
-            fuse = BN_FUSE_TAIL and (residual is None or (residual.dtype == torch.float32 and residual.shape == rows.shape))
-            y = BatchNormRowsFunction.apply(rows, bn.weight, bn.bias, bn.running_mean if track else None,
-                                            bn.running_var if track else None, float(momentum), float(bn.eps),
-                                            residual if fuse else None, bool(relu and fuse))
+        if _bn_on_kernels(bn, rows, rows.shape[1]):
+            fuse = BN_FUSE_TAIL and _residual_fits(residual, rows)      # else the norm on the kernels, the tail in torch
+            y = _bn_function(bn, rows, momentum, residual if fuse else None, bool(relu and fuse))
             return y if fuse else tail(y)
         return tail(torch.nn.functional.batch_norm(rows, bn.running_mean if not bn.training or bn.track_running_stats else None,
                                                    bn.running_var if not bn.training or bn.track_running_stats else None,
@@ -387,21 +402,15 @@ def bn_rows(bn, rows, grid, residual=None, relu=False, image=False, channels=Non
 
 def _bn_rows_padded(bn, rows, grid, residual, relu, image, C, relu_then_add):
     """``bn_rows`` for padded rows and / or the ReLU-then-add tail.  A plain BatchNorm under the conditions of ``bn_rows``' HIP branch
-    takes ``BatchNormRowsPaddedFunction``; everything else is ``bn_rows`` itself on the first ``C`` columns (a view), the tail in torch,
+    whose tail can ride in the passes takes ``BatchNormRowsFunction`` at padded width; everything else is ``bn_rows`` itself on the first ``C`` columns (a view), the tail in torch,
     zero columns behind.  The bookkeeping of ``num_batches_tracked`` and the momentum is the code above, reached either way."""
     if relu_then_add and (not relu or residual is None):
         raise ValueError("bn_rows: relu_then_add is relu(bn) + residual")
     ld = rows.shape[1]
-    plain = type(bn) in (torch.nn.BatchNorm3d, torch.nn.BatchNorm2d)
-    if (plain and (bn.training or (bn.running_mean is None and bn.running_var is None)) and TRAIN_CONV == "hip" and BN_ON_HIP and BN_FUSE_TAIL
-            and rows.is_cuda and rows.dtype == torch.float32 and C % 4 == 0 and ld % 4 == 0 and bn.weight is not None and bn.bias is not None
-            and rows.shape[0] > 1 and (residual is None or (residual.dtype == torch.float32 and residual.shape == rows.shape))):
-        from ..functions import BatchNormRowsPaddedFunction
-        momentum = _count_batch(bn)
-        track = bn.training and bn.track_running_stats
-        return BatchNormRowsPaddedFunction.apply(rows, bn.weight, bn.bias, bn.running_mean if track else None, bn.running_var if track else None,
-                                                 float(momentum), float(bn.eps), residual, 2 if relu_then_add else int(bool(relu)))
+    if _bn_on_kernels(bn, rows, C) and BN_FUSE_TAIL and _residual_fits(residual, rows):      # the padded entries need the fused tail
+        return _bn_function(bn, rows, _count_batch(bn), residual, 2 if relu_then_add else int(bool(relu)), C)
     res = None if residual is None else residual[:, :C]
+    plain = type(bn) in (torch.nn.BatchNorm3d, torch.nn.BatchNorm2d)
     x = rows[:, :C] if plain else rows[:, :C].contiguous()         # the other norms see an NCHW / NCDHW view of the rows
     if relu_then_add:
         y = bn_rows(bn, x, grid, relu=True, image=image) + res

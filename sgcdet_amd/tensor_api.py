@@ -1294,87 +1294,76 @@ class TensorOps:
         self._call("sgc_topk_select_ws", flat, n, int(k), idx, valid, mask, ws, wsb)
         return idx, valid, mask
 
-    def bn_rows_forward(self, x, weight, bias, running_mean=None, running_var=None, momentum=0.1, eps=1e-5, residual=None, relu=False):
-        """Training-mode BatchNorm over rows x [rows, C] -> (y, mean [C], invstd [C]); the running statistics are updated in
-        place as nn.BatchNorm does.  ``residual`` / ``relu``: y = relu(bn(x) + residual) in the same pass (``sgc_bn_rows_act_forward``)."""
+    def _bn_rows_fwd(self, who, padded, x, weight, bias, running_mean, running_var, momentum, eps, residual, tail):
+        """The checks, allocations and workspace of both ``bn_rows_*forward`` methods, then the entry the caller's form names."""
         self._check(x=x, weight=weight, bias=bias, running_mean=running_mean, running_var=running_var, residual=residual)
         self._f32(x=x, weight=weight, bias=bias, running_mean=running_mean, running_var=running_var, residual=residual)
-        rows, Cc = x.shape
-        if weight.numel() != Cc or bias.numel() != Cc or (residual is not None and residual.shape != x.shape):
-            raise RuntimeError("bn_rows_forward: inconsistent shapes")
+        rows, ld = x.shape
+        Cc = weight.numel()
+        if (bias.numel() != Cc or (Cc > ld if padded else Cc != ld) or (residual is not None and residual.shape != x.shape)
+                or (tail == 2 and residual is None) or any(t is not None and t.numel() != Cc for t in (running_mean, running_var))):
+            raise RuntimeError(f"{who}: inconsistent shapes")
         y = torch.empty_like(x)
         mean = torch.empty(Cc, dtype=torch.float32, device=x.device)
         invstd = torch.empty_like(mean)
         n = int(self.lib._dll.sgc_bn_rows_workspace_floats(rows, Cc))
         ws = torch.empty(max(n, 4), dtype=torch.float32, device=x.device)
-        if residual is None and not relu:
-            self._call("sgc_bn_rows_forward", x, weight, bias, running_mean, running_var, float(momentum), float(eps), y, mean, invstd, ws,
-                       ws.numel(), rows, Cc)
+        head, out = (x, weight, bias, running_mean, running_var, float(momentum), float(eps)), (y, mean, invstd, ws, ws.numel(), rows, Cc)
+        if padded:
+            self._call("sgc_bn_rows_padded_forward", *head, residual, int(tail), *out, ld)
+        elif residual is None and not tail:
+            self._call("sgc_bn_rows_forward", *head, *out)
         else:
-            self._call("sgc_bn_rows_act_forward", x, weight, bias, running_mean, running_var, float(momentum), float(eps), residual, int(bool(relu)),
-                       y, mean, invstd, ws, ws.numel(), rows, Cc)
+            self._call("sgc_bn_rows_act_forward", *head, residual, int(bool(tail)), *out)
         return y, mean, invstd
+
+    def _bn_rows_bwd(self, who, padded, x, dy, mean, invstd, weight, bias, y, tail, want_dresidual):
+        """Likewise for both ``bn_rows_*backward`` methods -> (dx, dweight, dbias, dresidual | None)."""
+        self._check(x=x, dy=dy, mean=mean, invstd=invstd, weight=weight, bias=bias, y=y)
+        self._f32(x=x, dy=dy, mean=mean, invstd=invstd, weight=weight, bias=bias, y=y)
+        rows, ld = x.shape
+        Cc = weight.numel()
+        if (dy.shape != x.shape or mean.numel() != Cc or invstd.numel() != Cc or (Cc > ld if padded else Cc != ld)
+                or (y is not None and y.shape != x.shape) or (bias is not None and bias.numel() != Cc) or (tail == 1 and y is None)
+                or (tail == 2 and bias is None)):
+            raise RuntimeError(f"{who}: inconsistent shapes")
+        dx = torch.empty_like(x)
+        dw = torch.empty(Cc, dtype=torch.float32, device=x.device)
+        db = torch.empty_like(dw)
+        dres = torch.empty_like(x) if want_dresidual else None
+        n = int(self.lib._dll.sgc_bn_rows_workspace_floats(rows, Cc))
+        ws = torch.empty(max(n, 4), dtype=torch.float32, device=x.device)
+        if padded:
+            self._call("sgc_bn_rows_padded_backward", x, dy, y if tail == 1 else None, mean, invstd, weight, bias if tail == 2 else None, dx, dw, db,
+                       dres, int(tail), ws, ws.numel(), rows, Cc, ld)
+        elif y is None and not want_dresidual:
+            self._call("sgc_bn_rows_backward", x, dy, mean, invstd, weight, dx, dw, db, ws, ws.numel(), rows, Cc)
+        else:
+            self._call("sgc_bn_rows_act_backward", x, dy, y, mean, invstd, weight, dx, dw, db, dres, ws, ws.numel(), rows, Cc)
+        return dx, dw, db, dres
+
+    def bn_rows_forward(self, x, weight, bias, running_mean=None, running_var=None, momentum=0.1, eps=1e-5, residual=None, relu=False):
+        """Training-mode BatchNorm over rows x [rows, C] -> (y, mean [C], invstd [C]); the running statistics are updated in
+        place as nn.BatchNorm does.  ``residual`` / ``relu``: y = relu(bn(x) + residual) in the same pass (``sgc_bn_rows_act_forward``)."""
+        return self._bn_rows_fwd("bn_rows_forward", False, x, weight, bias, running_mean, running_var, momentum, eps, residual, int(bool(relu)))
 
     def bn_rows_backward(self, x, dy, mean, invstd, weight, y_relu=None, want_dresidual=False):
         """-> (dx [rows, C], dweight [C], dbias [C]) of ``bn_rows_forward``; with ``y_relu`` (the forward's output when it ended in a
         ReLU) and / or ``want_dresidual`` -> (dx, dweight, dbias, dresidual) through ``sgc_bn_rows_act_backward``."""
-        self._check(x=x, dy=dy, mean=mean, invstd=invstd, weight=weight, y_relu=y_relu)
-        self._f32(x=x, dy=dy, mean=mean, invstd=invstd, weight=weight, y_relu=y_relu)
-        rows, Cc = x.shape
-        if dy.shape != x.shape or mean.numel() != Cc or invstd.numel() != Cc or weight.numel() != Cc or (y_relu is not None and y_relu.shape != x.shape):
-            raise RuntimeError("bn_rows_backward: inconsistent shapes")
-        dx = torch.empty_like(x)
-        dw = torch.empty(Cc, dtype=torch.float32, device=x.device)
-        db = torch.empty_like(dw)
-        n = int(self.lib._dll.sgc_bn_rows_workspace_floats(rows, Cc))
-        ws = torch.empty(max(n, 4), dtype=torch.float32, device=x.device)
-        if y_relu is None and not want_dresidual:
-            self._call("sgc_bn_rows_backward", x, dy, mean, invstd, weight, dx, dw, db, ws, ws.numel(), rows, Cc)
-            return dx, dw, db
-        dres = torch.empty_like(x) if want_dresidual else None
-        self._call("sgc_bn_rows_act_backward", x, dy, y_relu, mean, invstd, weight, dx, dw, db, dres, ws, ws.numel(), rows, Cc)
-        return dx, dw, db, dres
+        out = self._bn_rows_bwd("bn_rows_backward", False, x, dy, mean, invstd, weight, None, y_relu, 0 if y_relu is None else 1, want_dresidual)
+        return out[:3] if y_relu is None and not want_dresidual else out
 
     def bn_rows_padded_forward(self, x, weight, bias, running_mean=None, running_var=None, momentum=0.1, eps=1e-5, residual=None, tail=0):
         """Training-mode BatchNorm over rows x [rows, ld] of which the first C = weight.numel() columns are channels and the rest
         padding -> (y [rows, ld] with zero padding, mean [C], invstd [C]) (``sgc_bn_rows_padded_forward``,
         include/sgcdet_amd_depth_train.h).  ``tail`` 0: bn(x) + residual?; 1: relu(bn(x) + residual?); 2: relu(bn(x)) + residual."""
-        self._check(x=x, weight=weight, bias=bias, running_mean=running_mean, running_var=running_var, residual=residual)
-        self._f32(x=x, weight=weight, bias=bias, running_mean=running_mean, running_var=running_var, residual=residual)
-        rows, ld = x.shape
-        Cc = weight.numel()
-        if (bias.numel() != Cc or Cc > ld or (residual is not None and residual.shape != x.shape) or (tail == 2 and residual is None)
-                or any(t is not None and t.numel() != Cc for t in (running_mean, running_var))):
-            raise RuntimeError("bn_rows_padded_forward: inconsistent shapes")
-        y = torch.empty_like(x)
-        mean = torch.empty(Cc, dtype=torch.float32, device=x.device)
-        invstd = torch.empty_like(mean)
-        n = int(self.lib._dll.sgc_bn_rows_workspace_floats(rows, Cc))
-        ws = torch.empty(max(n, 4), dtype=torch.float32, device=x.device)
-        self._call("sgc_bn_rows_padded_forward", x, weight, bias, running_mean, running_var, float(momentum), float(eps), residual, int(tail),
-                   y, mean, invstd, ws, ws.numel(), rows, Cc, ld)
-        return y, mean, invstd
+        return self._bn_rows_fwd("bn_rows_padded_forward", True, x, weight, bias, running_mean, running_var, momentum, eps, residual, tail)
 
     def bn_rows_padded_backward(self, x, dy, mean, invstd, weight, bias=None, y=None, tail=0, want_dresidual=False):
         """-> (dx [rows, ld], dweight [C], dbias [C], dresidual [rows, ld] | None) of ``bn_rows_padded_forward``
         (``sgc_bn_rows_padded_backward``): ``y`` is the forward's output (tail 1 reads its gate there), ``bias`` the norm's (tail 2
         recomputes its gate from x).  Padding columns of dx and dresidual are zero."""
-        self._check(x=x, dy=dy, mean=mean, invstd=invstd, weight=weight, bias=bias, y=y)
-        self._f32(x=x, dy=dy, mean=mean, invstd=invstd, weight=weight, bias=bias, y=y)
-        rows, ld = x.shape
-        Cc = weight.numel()
-        if (dy.shape != x.shape or mean.numel() != Cc or invstd.numel() != Cc or Cc > ld or (y is not None and y.shape != x.shape)
-                or (bias is not None and bias.numel() != Cc) or (tail == 1 and y is None) or (tail == 2 and bias is None)):
-            raise RuntimeError("bn_rows_padded_backward: inconsistent shapes")
-        dx = torch.empty_like(x)
-        dw = torch.empty(Cc, dtype=torch.float32, device=x.device)
-        db = torch.empty_like(dw)
-        dres = torch.empty_like(x) if want_dresidual else None
-        n = int(self.lib._dll.sgc_bn_rows_workspace_floats(rows, Cc))
-        ws = torch.empty(max(n, 4), dtype=torch.float32, device=x.device)
-        self._call("sgc_bn_rows_padded_backward", x, dy, y if tail == 1 else None, mean, invstd, weight, bias if tail == 2 else None, dx, dw, db,
-                   dres, int(tail), ws, ws.numel(), rows, Cc, ld)
-        return dx, dw, db, dres
+        return self._bn_rows_bwd("bn_rows_padded_backward", True, x, dy, mean, invstd, weight, bias, y, tail, want_dresidual)
 
     def softmax_rows_backward(self, p, dp, C=None, ldg=None):
         """g = p * (dp - sum(p * dp)) over the first ``C`` columns of the rows p, dp (default: all of p's) -> g [rows, ldg] with

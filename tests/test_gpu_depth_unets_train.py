@@ -1,5 +1,5 @@
 """``DepthNet_Fusion``'s regulation U-Nets, ``depth_reg`` and the softmax in training on the HIP kernels
-(include/sgcdet_amd_depth_train.h, csrc/batch_norm.hip, csrc/softmax_rows.hip, functions.py ``BatchNormRowsPaddedFunction`` /
+(include/sgcdet_amd_depth_train.h, csrc/batch_norm.hip, csrc/softmax_rows.hip, functions.py ``BatchNormRowsFunction`` /
 ``PaddedConv2dFunction`` / ``ConvTranspose2dRowsFunction`` / ``DepthRegSoftmaxFunction``, plugin/conv_plan.py, plugin/depth_net.py,
 DESIGN.md 4.14b).
 
@@ -190,6 +190,19 @@ def test_padded_norm_nan_and_refusals(gpu_ops):
             bwd(*args)
     torch.cuda.synchronize()
     assert bool((y == 7.0).all())                                 # nothing was launched
+
+
+def test_dense_norm_backward_refuses_a_misaligned_weight(gpu_ops):
+    """The dense entries are the padded kernels at ld == C, whose backward apply pass reads weight, dweight and dbias with 16-byte
+    loads: ``sgc_bn_rows_act_backward`` with a weight pointer 4 bytes off is refused, and nothing is launched."""
+    from sgcdet_amd._abi import SgcError
+    x, ws = torch.zeros(8, 32).cuda(), torch.zeros(4096).cuda()
+    v = torch.ones(36).cuda()
+    dx, dw, db = torch.full((8, 32), 7.0).cuda(), torch.full((32,), 7.0).cuda(), torch.full((32,), 7.0).cuda()
+    with pytest.raises(SgcError, match="aligned"):
+        gpu_ops._call("sgc_bn_rows_act_backward", x, x, x, v[:32], v[:32], v[1:33], dx, dw, db, None, ws, 4096, 8, 32)
+    torch.cuda.synchronize()
+    assert bool((dx == 7.0).all()) and bool((dw == 7.0).all()) and bool((db == 7.0).all())      # nothing was launched
 
 
 # ---- 2. the softmax backward -------------------------------------------------------------------------------------------------------
