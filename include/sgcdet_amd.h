@@ -722,6 +722,8 @@ int sgc_pack_conv_weight_batch(const void *items, int n_items, int total_blocks,
  *   boxes [n,6] (x1,y1,z1,x2,y2,z2) fp32, labels [n] int64, order [n] int64 = argsort(scores) ASCENDING (the
  *   reference's `torch.argsort(scores)`; the best box is order[n-1]);  a lower-scored box is dropped when, against a
  *   kept box, NOT (iou * (same class) <= iou_thr) -- exactly the reference's comparison, NaN IoU included.
+ *   Ties: the entry processes `order` from its end, whatever it holds; the front end (TensorOps.aligned_nms3d) sorts
+ *   stably, so among equal scores the HIGHER box index is processed first, on every device.
  *   keep [n] int64 OUT: indices of the kept boxes in descending score (the reference's return value),
  *   n_keep [1] int32 OUT (device), workspace >= n * ceil(n/64) uint64.  n <= 4096.                       */
 int sgc_aligned_nms3d(const float *boxes, const int64_t *order, const int64_t *labels, float iou_thr,
@@ -734,6 +736,8 @@ int sgc_aligned_nms3d(const float *boxes, const int64_t *order, const int64_t *l
  * SunRgbdImVoxelHeadV2._nms, mmdet3d_plugin/models/dense_heads/imvoxel_head_v2.py:565-584 (ARKit configs):
  *   boxes  [K,5] fp32 (x1, y1, x2, y2, ry) = `mlvl_bboxes_for_nms`; converted to (xc, yc, w, h, ry) as :256-262;
  *   order  [C,K] int64: row c = box indices by DESCENDING score of class c (`_scores.sort(0, descending=True)`);
+ *   ties: the front end (TensorOps.nms_rotated_bev) sorts stably, so among equal scores the LOWER box index is
+ *   processed first; box3d_multiclass_nms_rotated cuts to max_num by a stable sort too (lower class, then rank, stays);
  *   counts [C] int32 (device): only the first counts[c] entries of row c are candidates (score > score_thr);
  *   a candidate is dropped when a kept, better-scored one of the same class has IoU > iou_thr (exact
  *   intersection polygon of the two rotated rectangles, fp32, the reference kernel's operation order);

@@ -372,7 +372,8 @@ class SunRgbdImVoxelHeadV2(ImVoxelHeadV2):
 def box3d_multiclass_nms_rotated(ops, bboxes, scores, score_thr, max_num, nms_thr):
     """mmdet3d ``box3d_multiclass_nms`` (box3d_nms.py:8-128) with ``cfg.use_rotate_nms`` as the ARKit head calls it:
     bboxes [K,7] (cx,cy,cz,w,l,h,yaw), scores [K,C] -> (boxes [n,7], scores [n], labels [n]) concatenated class by
-    class, each class in descending score; more than ``max_num`` survivors: the best ``max_num`` by score.
+    class, each class in descending score; more than ``max_num`` survivors: the best ``max_num`` by score, by a
+    stable sort -- among equal scores at the cut the lower class, then the earlier survivor of that class, stays.
     ``ops``: a TensorOps (the HIP library in the product, the CPU oracle in tests).  One host read-back (the
     per-class survivor counts) -- the outputs are variable-length."""
     K, C = scores.shape
@@ -386,7 +387,7 @@ def box3d_multiclass_nms_rotated(ops, bboxes, scores, score_thr, max_num, nms_th
     labels = torch.arange(C, device=keep.device)[:, None].expand(C, K)[live]
     out_boxes, out_scores = bboxes[sel], scores[sel, labels]
     if out_boxes.shape[0] > max_num:
-        _, inds = out_scores.sort(descending=True)
+        _, inds = out_scores.sort(descending=True, stable=True)
         inds = inds[:max_num]
         out_boxes, out_scores, labels = out_boxes[inds], out_scores[inds], labels[inds]
     return out_boxes, out_scores, labels

@@ -1415,7 +1415,9 @@ class TensorOps:
     # ---- 8. post-processing ----------------------------------------------------------------
     def aligned_nms3d(self, boxes, scores, labels, iou_thr):
         """mmdet3d ``aligned_3d_nms(boxes [n,6], scores [n], classes [n], thresh)`` -> kept indices (int64,
-        descending score).  One host read-back (the number of kept boxes) -- this is post-processing."""
+        descending score).  One host read-back (the number of kept boxes) -- this is post-processing.
+        Tie rule: the sort is the reference's ascending argsort made stable, and boxes are processed from its end --
+        among equal scores the HIGHER index is processed first (it is kept, and it suppresses the lower ones)."""
         self._check(boxes=boxes, scores=scores, labels=labels)
         self._f32(boxes=boxes, scores=scores)
         n = boxes.shape[0]
@@ -1426,7 +1428,7 @@ class TensorOps:
         n_keep = torch.zeros(1, dtype=torch.int32, device=boxes.device)
         if n == 0:
             return keep
-        order = torch.argsort(scores)                              # the reference's call: ascending
+        order = torch.argsort(scores, stable=True)                 # the reference's call (ascending), ties pinned
         ws = torch.empty(n * ((n + 63) // 64), dtype=torch.int64, device=boxes.device)
         self._call("sgc_aligned_nms3d", boxes, order, labels, float(iou_thr), keep, n_keep, ws, n)
         return keep[: int(n_keep.item())]
@@ -1435,7 +1437,7 @@ class TensorOps:
         """The class loop of mmdet3d ``box3d_multiclass_nms`` (box3d_nms.py:52-68) with ``use_rotate_nms``: for
         every class c, ``nms_bev(boxes[scores[:, c] > score_thr], ...)``.  boxes [K,5] (x1,y1,x2,y2,ry), scores
         [K,C].  Returns (keep [C,K] int64: kept box indices per class in descending score, n_keep [C] int32);
-        nothing is read back to the host here."""
+        nothing is read back to the host here.  Tie rule: among equal scores the LOWER index is processed first."""
         self._check(boxes=boxes, scores=scores)
         self._f32(boxes=boxes, scores=scores)
         K, C = scores.shape
