@@ -8,7 +8,8 @@ points of ``include/sgcdet_amd_train.h`` have a table of their own
 asked for it (the product library; the oracle has no twin of them); the image-side
 convolutions of ``include/sgcdet_amd_image.h`` likewise (``IMAGE_SIGNATURES`` /
 ``IMAGE_INTROSPECTION``); ``include/sgcdet_amd_depth_train.h`` (``DEPTH_TRAIN_SIGNATURES`` /
-``DEPTH_TRAIN_INTROSPECTION``) is bound together with the training tables.  Nothing
+``DEPTH_TRAIN_INTROSPECTION``) and ``include/sgcdet_amd_level_train.h`` (``LEVEL_TRAIN_SIGNATURES`` /
+``LEVEL_TRAIN_INTROSPECTION``) are bound together with the training tables.  Nothing
 here touches torch; pointers are plain integers (``tensor.data_ptr()``).
 """
 import ctypes as C
@@ -137,6 +138,19 @@ DEPTH_TRAIN_SIGNATURES = {
 
 DEPTH_TRAIN_INTROSPECTION = {}      # the padded norm sizes its workspace with sgc_bn_rows_workspace_floats (INTROSPECTION)
 
+# include/sgcdet_amd_level_train.h: the backward halves of a view-transform level in training -- LayerNorm, sampling locations /
+# attention weights, mean over views (no CPU-oracle twin; bound with the training tables)
+LEVEL_TRAIN_SIGNATURES = {
+    "sgc_layer_norm_rows_backward": [_p, _p, _f] + [_p] * 5 + [C.c_int64, _i, _i, _p],
+    "sgc_sampling_locations_forward": [_p] * 5 + [_i] * 5 + [_p],
+    "sgc_sampling_locations_backward": [_p] * 5 + [_i] * 5 + [_p],
+    "sgc_view_mean_backward": [_p] * 4 + [_i] * 5 + [_p],
+}
+
+LEVEL_TRAIN_INTROSPECTION = {
+    "sgc_layer_norm_rows_backward_workspace_floats": (C.c_int64, [_i] * 2),
+}
+
 # include/sgcdet_amd_image.h: the 2-D convolutions of the image-side CNNs (no CPU-oracle twin)
 IMAGE_SIGNATURES = {
     "sgc_conv2d_nhwc_ex_bf16x3": [_p] * 7 + [_i] * 13 + [_p],
@@ -175,14 +189,14 @@ class Library:
 
     def __init__(self, path, train=False, image=False):
         """``train`` / ``image``: also bind (and require) the entry points of include/sgcdet_amd_train.h and
-        include/sgcdet_amd_depth_train.h / of include/sgcdet_amd_image.h."""
+        include/sgcdet_amd_depth_train.h, include/sgcdet_amd_level_train.h / of include/sgcdet_amd_image.h."""
         self.path = str(path)
         self._dll = C.CDLL(self.path)
         missing = []
         signatures = {**SIGNATURES, **(TRAIN_SIGNATURES if train else {}), **(DEPTH_TRAIN_SIGNATURES if train else {}),
-                      **(IMAGE_SIGNATURES if image else {})}
+                      **(LEVEL_TRAIN_SIGNATURES if train else {}), **(IMAGE_SIGNATURES if image else {})}
         introspection = {**INTROSPECTION, **(TRAIN_INTROSPECTION if train else {}), **(DEPTH_TRAIN_INTROSPECTION if train else {}),
-                         **(IMAGE_INTROSPECTION if image else {})}
+                         **(LEVEL_TRAIN_INTROSPECTION if train else {}), **(IMAGE_INTROSPECTION if image else {})}
         for name, argtypes in signatures.items():
             try:
                 fn = getattr(self._dll, name)

@@ -838,8 +838,105 @@ class LinearRowsFunction(Function):
             dwk = ops.conv3d_wgrad_bf16x3(x, _pad_cols(dy, 4).contiguous(), (x.shape[0], 1, 1), 1, 1)     # [1, cout_p, cin]
             dw = dwk[0, :cout].to(weight.dtype)
         if ctx.has_bias and ctx.needs_input_grad[2]:
-            db = dy.sum(0)
+            # the fused level (plugin/voxformer.py TRAIN_LEVEL_FUSED) takes the fixed-order column sums of this library; the
+            # default path keeps dy.sum(0), so its summation order does not move
+            db = ops.rows_colsum(dy) if level_fused_enabled() and dy.is_cuda and cout % 4 == 0 and dy.shape[0] > 0 else dy.sum(0)
         return dx, dw, db
+
+
+def level_fused_enabled():
+    from .plugin.voxformer import TRAIN_LEVEL_FUSED
+    return bool(TRAIN_LEVEL_FUSED["enabled"])
+
+
+class LayerNormRowsFunction(Function):
+    """``F.layer_norm(x, (C,), gamma, beta, eps)`` over rows x [rows, C]: the forward is the inference kernel
+    (``sgc_layer_norm_rows``), the backward ``sgc_layer_norm_rows_backward``, which recomputes the row statistics from x."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps):
+        x, gamma, beta = x.float().contiguous(), gamma.float().contiguous(), beta.float().contiguous()
+        ctx.save_for_backward(x, gamma)
+        ctx.eps = float(eps)
+        return ext.ops().layer_norm_rows(x, gamma, beta, ctx.eps)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        x, gamma = ctx.saved_tensors
+        if x.shape[0] == 0:
+            return torch.zeros_like(x), torch.zeros_like(gamma), torch.zeros_like(gamma), None
+        dx, dgamma, dbeta = ext.ops().layer_norm_rows_backward(x, gamma, dy.float().contiguous(), ctx.eps)
+        return dx, dgamma, dbeta, None
+
+
+class SamplingLocationsFunction(Function):
+    """``apply(ref, proj, normalizer, M, L, P)`` -> (loc [n, M, L, P, 3], attn [n, M, L, P]): the sampling locations and the
+    attention softmax of the deformable attention from the concatenated [uv | depth | logits] projection, in the
+    layouts ``PairListDeformAttnFunction`` takes.  Saves attn only; ref and normalizer take no gradient."""
+
+    @staticmethod
+    def forward(ctx, ref, proj, normalizer, M, L, P):
+        ref, proj, normalizer = ref.float().contiguous(), proj.float().contiguous(), normalizer.float().contiguous()
+        ctx.ldp = proj.shape[1]
+        if proj.shape[0] == 0:
+            loc, attn = proj.new_zeros((0, M, L, P, 3)), proj.new_zeros((0, M, L, P))
+        else:
+            loc, attn = ext.ops().sampling_locations_forward(ref, proj, normalizer, M, L, P)
+        ctx.save_for_backward(attn, normalizer)
+        return loc, attn
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loc, grad_attn):
+        attn, normalizer = ctx.saved_tensors
+        if attn.shape[0] == 0:
+            return None, attn.new_zeros((0, ctx.ldp)), None, None, None, None
+        grad_loc = torch.zeros(attn.shape + (3,), dtype=attn.dtype, device=attn.device) if grad_loc is None else grad_loc.float().contiguous()
+        grad_attn = torch.zeros_like(attn) if grad_attn is None else grad_attn.float().contiguous()
+        return None, ext.ops().sampling_locations_backward(attn, grad_loc, grad_attn, normalizer, ctx.ldp), None, None, None, None
+
+
+class ViewMeanFunction(Function):
+    """``apply(per_pair, slot, valid_index, n_valid)`` -> [n_valid, C]: the mean of a voxel's pair rows over the cameras that see
+    it (``sgc_view_mean``: the cameras are added in camera order, unlike ``index_add``) and ``sgc_view_mean_backward``."""
+
+    @staticmethod
+    def forward(ctx, per_pair, slot, valid_index, n_valid):
+        per_pair = per_pair.float().contiguous()
+        ctx.save_for_backward(slot, valid_index)
+        ctx.n_pairs = per_pair.shape[0]
+        if n_valid == 0 or per_pair.shape[0] == 0:
+            return per_pair.new_zeros((n_valid, per_pair.shape[1]))
+        return ext.ops().view_mean(per_pair, slot, valid_index, n_valid)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_mean):
+        slot, valid_index = ctx.saved_tensors
+        if grad_mean.shape[0] == 0 or ctx.n_pairs == 0:
+            return grad_mean.new_zeros((ctx.n_pairs, grad_mean.shape[1])), None, None, None
+        return ext.ops().view_mean_backward(grad_mean.float().contiguous(), slot, valid_index, ctx.n_pairs), None, None, None
+
+
+class ScatterRowsFunction(Function):
+    """``apply(rows, valid_index, Nq)`` -> [Nq, C]: zeros with ``rows`` at the voxels ``valid_index`` (int32, each at most once):
+    a zero fill and ``sgc_scatter_rows``; the backward is the gather of those rows (one ``index_select``)."""
+
+    @staticmethod
+    def forward(ctx, rows, valid_index, Nq):
+        rows = rows.float().contiguous()
+        ctx.save_for_backward(valid_index)
+        vol = torch.zeros((Nq, rows.shape[1]), dtype=torch.float32, device=rows.device)
+        if rows.shape[0]:
+            ext.ops().scatter_rows(rows, valid_index, vol)
+        return vol
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_vol):
+        valid_index, = ctx.saved_tensors
+        return grad_vol.index_select(0, valid_index), None, None
 
 
 def linear_rows(module, x):

@@ -77,6 +77,21 @@ GEO_LINEAR_FUSED = __import__("os").environ.get("SGC_GEO_LINEAR", "1") != "0"
 TRAIN_BWD_TILED = dict(enabled=True, bin=(8, 22), halo=(2, 2))       # 12 x 26-pixel windows: 79 KB of LDS at Cm = 32, two workgroups per CU (sweep: profiles/r06_bwd_tile_bench_cfg2.txt)
 
 
+# The small stages of a TRAINING level on this library's kernels (include/sgcdet_amd_level_train.h): LayerNorm forward
+# + backward, ONE concatenated [uv | depth | logits] projection with the sampling locations and the attention softmax behind it in
+# one launch each way, the mean over views without float atomics, the slot scatter.  OPT-IN (env SGC_LEVEL_TRAIN_FUSED=1, or flip the
+# entry inside a process); it takes effect under autograd on CUDA fp32 tensors with TRAIN_CONV == "hip" on the pair-list path only.
+TRAIN_LEVEL_FUSED = dict(enabled=__import__("os").environ.get("SGC_LEVEL_TRAIN_FUSED", "0") == "1")
+
+
+def _level_fused(x):
+    """Does the fused training level apply to the tensor ``x``?"""
+    if not TRAIN_LEVEL_FUSED["enabled"] or not torch.is_grad_enabled() or not x.is_cuda or x.dtype != torch.float32:
+        return False
+    from .conv_plan import TRAIN_CONV, train_products_ok
+    return TRAIN_CONV == "hip" and train_products_ok()
+
+
 def _tiled_env_overrides():
     """Sweeps without editing the file: SGC_TILED=0|1, SGC_TILED_CM32 / SGC_TILED_CM16 = "bin_w,bin_h,halo_x,halo_y,depth_in_lds"."""
     import os
@@ -540,7 +555,9 @@ class DeformCrossAttention_DFA3D(BaseModule):
                 bins = (pc["bin_offset"], H, W, bw, bh, tuple(TRAIN_BWD_TILED["halo"]), shift)
         n_pairs, n_valid = pc["totals"][:2].tolist()                 # the level's one host sync
         cam, q = pc["pair_cam"][:n_pairs].long(), pc["pair_q"][:n_pairs].long()     # camera-major; inside a camera by bin, or ascending q
-        valid_index = pc["valid_index"][:n_valid].long()
+        from .conv_plan import TRAIN_CONV
+        fused = _level_fused(feat) and C % 32 == 0          # TRAIN_LEVEL_FUSED: the int32 valid_index of the kernels serves throughout
+        valid_index = None if fused else pc["valid_index"][:n_valid].long()
         count = pc["vox_count"]
         shapes3 = da.get_spatial_shape_3D(spatial_shapes, dist.shape[-1])
         ref = ref_cam[cam, q]                                          # [n_pairs, 3]
@@ -549,7 +566,23 @@ class DeformCrossAttention_DFA3D(BaseModule):
                                                ref.view(n_pairs, 1, 1, 1, 3).expand(n_pairs, 1, L, 1, 3).contiguous()
                                                if L > 1 else ref.view(n_pairs, 1, 1, 1, 3),
                                                torch.ones((n_pairs, 1, L, 1), dtype=feat.dtype, device=feat.device), item, bins)
-        if self.deformable_attn:
+        if self.deformable_attn and fused:
+            # ONE projection of geo -- [uv | depth | logits], the rows of raw_projection -- and one launch from it to loc / attn
+            from ..functions import LinearRowsFunction, SamplingLocationsFunction, train_weight_planes
+            # (the 2-D classes' sampling_offsets_depth is a _ZeroLinear: zeros that are no parameter and take no gradient)
+            w = torch.cat([da.sampling_offsets.weight, da.sampling_offsets_depth.weight, da.attention_weights.weight], 0)
+            b = torch.cat([da.sampling_offsets.bias, da.sampling_offsets_depth.bias, da.attention_weights.bias], 0)
+            if n_pairs >= 128:
+                train_weight_planes().mark_ephemeral(w)
+                proj = LinearRowsFunction.apply(geo, w, b)
+            else:
+                proj = F.linear(geo, w, b)
+            normalizer = torch.stack([shapes3[..., 1], shapes3[..., 0], shapes3[..., 2]], -1).to(feat.dtype)   # (W, H, D) per level
+            loc, attn = SamplingLocationsFunction.apply(ref, proj, normalizer, M, L, P)
+            per_pair = PairListDeformAttnFunction.apply(value, dist.view(N, S, 1, -1), shapes3, level_start_index, loc, attn, item, bins)
+            if self.geo_residual:
+                per_pair = per_pair + geo
+        elif self.deformable_attn:
             off_uv = linear_rows(da.sampling_offsets, geo).view(n_pairs, M, L, P, 2)
             off_d = (geo.new_zeros((n_pairs, M, L, P, 1)) if isinstance(da.sampling_offsets_depth, _ZeroLinear)
                      else linear_rows(da.sampling_offsets_depth, geo).view(n_pairs, M, L, P, 1))
@@ -561,15 +594,19 @@ class DeformCrossAttention_DFA3D(BaseModule):
                 per_pair = per_pair + geo
         else:
             per_pair = geo
-        from .conv_plan import TRAIN_CONV
         if TRAIN_CONV == "hip" and C % 32 == 0:
             # inter-view aggregation on the pair list as well: no dense [N, L, C] slots (262 MB at config 2), K/V in-projected
             # for visible pairs only, the softmax over views and its backward on sgc_view_attend(_backward)
             from ..functions import LinearRowsFunction, ViewAttendFunction, linear_rows
             slot = pc["slot"]                        # (camera, voxel) -> pair row (in the binned order when binned), -1 = not visible
-            row_of = pc["row_of"].long()             # voxel -> compact row of `valid_index`, -1 = seen by no camera
-            mean = torch.zeros((n_valid, C), dtype=per_pair.dtype, device=feat.device).index_add(0, row_of[q], per_pair)
-            pooled = linear_rows(self.output_proj, mean / count[valid_index][:, None])
+            if fused:
+                from ..functions import ViewMeanFunction
+                mean = ViewMeanFunction.apply(per_pair, slot, pc["valid_index"][:n_valid], n_valid)     # cameras added in camera order
+                pooled = linear_rows(self.output_proj, mean)
+            else:
+                row_of = pc["row_of"].long()         # voxel -> compact row of `valid_index`, -1 = seen by no camera
+                mean = torch.zeros((n_valid, C), dtype=per_pair.dtype, device=feat.device).index_add(0, row_of[q], per_pair)
+                pooled = linear_rows(self.output_proj, mean / count[valid_index][:, None])
             if self.inter_view_aggregation == "attn":
                 mha = self.attention_pooling
                 w, b = mha.in_proj_weight, mha.in_proj_bias
@@ -586,6 +623,9 @@ class DeformCrossAttention_DFA3D(BaseModule):
             if self.inter_view_aggregation == "attn":
                 pooled, _ = self.attention_pooling(pooled[None], valid_slots, valid_slots, ~valid_mask.t())
                 pooled = pooled[0]
+        if fused:
+            from ..functions import ScatterRowsFunction
+            return self.dropout(ScatterRowsFunction.apply(pooled, pc["valid_index"][:n_valid], Nq).view(1, Nq, C)) + query
         out = torch.zeros((1, Nq, C), dtype=feat.dtype, device=feat.device)
         out = out.index_put((torch.zeros_like(valid_index), valid_index), pooled)
         return self.dropout(out) + query
@@ -879,6 +919,11 @@ def _layer_norm(norm, x):
             and norm.elementwise_affine and len(norm.normalized_shape) == 1 and x.is_contiguous()):
         C = norm.normalized_shape[0]
         return _ops().layer_norm_rows(x.view(-1, C), norm.weight, norm.bias, norm.eps).view(x.shape)
+    if (isinstance(norm, nn.LayerNorm) and norm.elementwise_affine and len(norm.normalized_shape) == 1 and x.is_contiguous()
+            and _level_fused(x)):
+        from ..functions import LayerNormRowsFunction
+        C = norm.normalized_shape[0]
+        return LayerNormRowsFunction.apply(x.view(-1, C), norm.weight, norm.bias, norm.eps).view(x.shape)
     return norm(x)
 
 

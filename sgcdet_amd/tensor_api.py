@@ -1392,6 +1392,68 @@ class TensorOps:
             self._call("sgc_layer_norm_rows", x, gamma, beta, float(eps), y, count, rows, Cc)
         return y
 
+    # ---- 7c. a view-transform level in training (include/sgcdet_amd_level_train.h) --------------
+    def layer_norm_rows_backward(self, x, gamma, dy, eps=1e-5):
+        """-> (dx [rows, C], dgamma [C], dbeta [C]) of ``layer_norm_rows`` (``sgc_layer_norm_rows_backward``): the row statistics
+        are recomputed from x."""
+        self._check(x=x, gamma=gamma, dy=dy)
+        self._f32(x=x, gamma=gamma, dy=dy)
+        if x.dim() != 2 or dy.shape != x.shape or gamma.numel() != x.shape[1]:
+            raise RuntimeError("layer_norm_rows_backward: inconsistent shapes")
+        rows, Cc = x.shape
+        dx = torch.empty_like(x)
+        dgamma = torch.empty(Cc, dtype=torch.float32, device=x.device)
+        dbeta = torch.empty_like(dgamma)
+        if rows == 0:
+            return dx, dgamma.zero_(), dbeta.zero_()
+        n = int(self.lib._dll.sgc_layer_norm_rows_backward_workspace_floats(rows, Cc))
+        if n < 0:
+            raise RuntimeError("layer_norm_rows_backward: " + self.lib.last_error())
+        ws = torch.empty(n, dtype=torch.float32, device=x.device)
+        self._call("sgc_layer_norm_rows_backward", x, gamma, float(eps), dy, dx, dgamma, dbeta, ws, n, rows, Cc)
+        return dx, dgamma, dbeta
+
+    def sampling_locations_forward(self, ref, proj, normalizer, M, L, P):
+        """ref [n, 3], proj [n, ldp] = [uv (m, l, p, 2) | depth | logits | unread padding], normalizer [L, 3] = (W, H, D) ->
+        (loc [n, M, L, P, 3], attn [n, M, L, P]): what ``dfa3d_forward_items`` takes (``sgc_sampling_locations_forward``)."""
+        self._check(ref=ref, proj=proj, normalizer=normalizer)
+        self._f32(ref=ref, proj=proj, normalizer=normalizer)
+        n, ldp = proj.shape
+        if ref.shape != (n, 3) or normalizer.shape != (L, 3) or ldp < 4 * M * L * P:
+            raise RuntimeError("sampling_locations_forward: inconsistent shapes")
+        loc = torch.empty((n, M, L, P, 3), dtype=torch.float32, device=proj.device)
+        attn = torch.empty((n, M, L, P), dtype=torch.float32, device=proj.device)
+        if n:
+            self._call("sgc_sampling_locations_forward", ref, proj, normalizer, loc, attn, n, M, L, P, ldp)
+        return loc, attn
+
+    def sampling_locations_backward(self, attn, grad_loc, grad_attn, normalizer, ldp):
+        """-> grad_proj [n, ldp] of ``sampling_locations_forward``, zero behind its 4 M L P columns (``sgc_sampling_locations_backward``)."""
+        self._check(attn=attn, grad_loc=grad_loc, grad_attn=grad_attn, normalizer=normalizer)
+        self._f32(attn=attn, grad_loc=grad_loc, grad_attn=grad_attn, normalizer=normalizer)
+        n, M, L, P = attn.shape
+        if grad_loc.shape != (n, M, L, P, 3) or grad_attn.shape != attn.shape or normalizer.shape != (L, 3) or ldp < 4 * M * L * P:
+            raise RuntimeError("sampling_locations_backward: inconsistent shapes")
+        grad_proj = torch.empty((n, ldp), dtype=torch.float32, device=attn.device)
+        if n:
+            self._call("sgc_sampling_locations_backward", attn, grad_loc, grad_attn, normalizer, grad_proj, n, M, L, P, ldp)
+        return grad_proj
+
+    def view_mean_backward(self, grad_mean, slot, valid_index, n_pairs):
+        """-> grad_feat [n_pairs, C] of ``view_mean`` (``sgc_view_mean_backward``); ``slot`` must hold each of the n_pairs rows
+        exactly once under a voxel of ``valid_index`` (compact_pairs / bin_pairs): every row is then written exactly once."""
+        self._check(grad_mean=grad_mean, slot=slot, valid_index=valid_index)
+        self._f32(grad_mean=grad_mean)
+        self._i32(slot=slot, valid_index=valid_index)
+        N, Nq = slot.shape
+        n_valid, Cc = grad_mean.shape
+        if valid_index.numel() != n_valid:
+            raise RuntimeError("view_mean_backward: inconsistent shapes")
+        grad_feat = torch.empty((n_pairs, Cc), dtype=torch.float32, device=grad_mean.device)
+        if n_valid and n_pairs:
+            self._call("sgc_view_mean_backward", grad_mean, slot, valid_index, grad_feat, N, Nq, Cc, n_valid, n_pairs)
+        return grad_feat
+
     def mask_dilate3(self, mask, grid):
         """3x3x3 dilation of a uint8 {0,1} voxel mask [X*Y*Z]."""
         self._check(mask=mask)

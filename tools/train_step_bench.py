@@ -24,6 +24,10 @@ ap.add_argument("--optimizer", default="none", choices=["none", "torch", "fused"
 ap.add_argument("--real-loss", action="store_true",
                 help="train against forward_train_from_features with 30 seeded boxes (target assignment + the head's three losses + the "
                      "occupancy loss) instead of the dummy quadratic loss; SGC_HEAD_LOSS_FUSED=0 / 1 selects the torch / fused head loss")
+ap.add_argument("--level-fused", default=None, choices=["0", "1", "ab"],
+                help="plugin/voxformer.py TRAIN_LEVEL_FUSED (DESIGN.md 4.19): 0 / 1 set the switch for the run; ab alternates the two settings block "
+                     "by block in this one process and reports, per setting, the median and the spread of the blocks of 10 steps and the kernel "
+                     "launches of a step (all, and those not of this library); with --sites also each setting's table")
 ap.add_argument("--glue", action="store_true", help="attribute the torch glue ops (copy / add / fill / sum / mul ...) to source lines of this package")
 args = ap.parse_args()
 w = workload(args.workload)
@@ -44,6 +48,15 @@ if args.real_loss:
     gt_boxes, gt_labels = gt_boxes.cuda(), (gt_labels % w["n_classes"]).cuda()
 
 update = [None]      # the parameter update of --optimizer, called after the backward
+
+
+def set_level_fused(on):
+    from sgcdet_amd.plugin import voxformer
+    voxformer.TRAIN_LEVEL_FUSED["enabled"] = bool(on)
+
+
+if args.level_fused in ("0", "1"):
+    set_level_fused(args.level_fused == "1")
 
 def step():
     for p in params:
@@ -118,7 +131,7 @@ if args.profile:
     print("by launch count (the step is launch-bound on the host):", file=sys.stderr)
     for e in sorted(allrows, key=lambda e: -e.count)[:25]:
         print(f"    x{e.count // 2:<5d} {e.device_time_total / 2e3:9.3f} ms/step  {e.key[:110]}", file=sys.stderr)
-if args.sites:
+def sites_table(label=""):
     import collections, traceback
     from torch.utils._python_dispatch import TorchDispatchMode
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -128,7 +141,8 @@ if args.sites:
         def __torch_dispatch__(self, func, types, a=(), kw=None):
             out = func(*a, **(kw or {}))
             name = func.__name__ if hasattr(func, "__name__") else str(func)
-            if any(k in name for k in ("fill", "zero", "copy", "add", "cat", "sum", "mul", "div", "index", "clone", "contiguous", "to_copy")):
+            if any(k in name for k in ("fill", "zero", "copy", "add", "cat", "sum", "mul", "div", "index", "clone", "contiguous", "to_copy",
+                                       "softmax", "layer_norm", "stack")):
                 fr = [f for f in traceback.extract_stack() if f.filename.startswith(root) and "/tools/" not in f.filename]
                 where = f"{os.path.relpath(fr[-1].filename, root)}:{fr[-1].lineno}" if fr else "(no frame of this package)"
                 shape = tuple(out.shape) if isinstance(out, torch.Tensor) else ()
@@ -138,9 +152,52 @@ if args.sites:
     with Sites():
         step()
     torch.cuda.synchronize()
-    print("torch ops of one step by issuing line (count, op, line, result shape):", file=sys.stderr)
+    print(f"torch ops of one step{label} by issuing line (count, op, line, result shape):", file=sys.stderr)
     for (name, where, shape), n in sorted(seen.items(), key=lambda kv: (-kv[1], kv[0][1])):
         print(f"  x{n:<4d} {name:28s} {where:46s} {shape}", file=sys.stderr)
+
+
+def launches_per_step():
+    """Launches of one step as torch.profiler sees them: every kernel; the kernels torch's own ops issue (``at::`` kernels and the BLAS /
+    convolution libraries' -- the rest is this library's); the memory copies / fills the runtime issues as such."""
+    from torch.profiler import profile, ProfilerActivity
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        for _ in range(2):
+            step()
+        torch.cuda.synchronize()
+    rows = [e for e in prof.key_averages() if not e.key.startswith("hip")]          # (the runtime's API rows count every launch again)
+    mem = sum(e.count for e in rows if e.key.startswith(("Memcpy", "Memset")))
+    aten = sum(e.count for e in rows if "at::" in e.key or e.key.startswith("Cijk") or "rocblas" in e.key.lower() or "miopen" in e.key.lower())
+    total = sum(e.count for e in rows) - mem
+    return dict(kernels=total // 2, aten=aten // 2, memcpy_memset=mem // 2)
+
+
+level_ab = None
+if args.level_fused == "ab":
+    blocks = {0: [], 1: []}
+    for v in (0, 1):
+        set_level_fused(v)
+        for _ in range(2):
+            step()
+    for b in range(max(2, (args.steps + 9) // 10)):
+        for v in ((0, 1) if b % 2 == 0 else (1, 0)):              # the two settings alternate, and so does which of them goes first
+            set_level_fused(v)
+            torch.cuda.synchronize(); t = time.perf_counter()
+            for _ in range(10):
+                step()
+            torch.cuda.synchronize()
+            blocks[v].append((time.perf_counter() - t) / 10 * 1e3)
+    level_ab = {}
+    for v in (0, 1):
+        set_level_fused(v)
+        bs = sorted(blocks[v])
+        level_ab[str(v)] = dict(ms_per_step_median=round(bs[len(bs) // 2], 3), ms_per_step_min=round(bs[0], 3), ms_per_step_max=round(bs[-1], 3),
+                                blocks=len(bs), launches_per_step=launches_per_step())
+        if args.sites:
+            sites_table(f" with TRAIN_LEVEL_FUSED = {bool(v)}")
+    set_level_fused(0)
+elif args.sites:
+    sites_table()
 if args.cprofile:
     import cProfile, pstats, io
     pr = cProfile.Profile()
@@ -200,4 +257,4 @@ if args.glue:
 print(json.dumps(dict(workload=args.workload, ms_per_step=ms_step, ms_per_step_best_block=ms_min, loss=l, params_with_grad=f"{n_grads}/{len(params)}",
                       peak_mem_gb=round(torch.cuda.max_memory_allocated() / 2**30, 2), no_neck=args.no_neck,
                       input_layout=args.input_layout, optimizer=args.optimizer, optimizer_variant=optimizer_variant,
-                      torch_variants_ms=variants_ms)))
+                      torch_variants_ms=variants_ms, level_fused=level_ab if level_ab is not None else args.level_fused)))
