@@ -8,7 +8,7 @@ the existing parametrisations of each kernel.
 
 Left out on purpose: the deformable-gather, plane-sweep and attention kernels (dfa3d_*, pairs_*, plane_sweep_*, view_attend*).
 Their reference semantics are the reference project's CUDA kernels, not torch, and their edge behaviour has contract tests of its own
-(tests/gather_edge_contract.py, tests/plane_sweep_grad_contract.py)."""
+(tests/gather_edge_contract.py; tests/plane_sweep_edge_contract.py, which places pz == 0, +-inf, NaN and huge positions)."""
 import pytest
 import torch
 import torch.nn.functional as F
