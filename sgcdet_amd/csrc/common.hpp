@@ -24,6 +24,14 @@ inline int check_launch(const char *what) {
 
 inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
+// workgroups of a grid-stride kernel over `work` items: at most 16 per CU
+inline int grid_for(int64_t work, int block) {
+  int64_t g = (work + block - 1) / block;
+  if (g > 256 * 16) g = 256 * 16;
+  if (g < 1) g = 1;
+  return (int)g;
+}
+
 // The ReLU of every epilogue.  torch.relu(NaN) is NaN and the oracle keeps it too (`v < 0 ? 0 : v`); fmaxf(NaN, 0) is 0, which
 // turns a poisoned activation into a clean zero that no loss ever sees (DESIGN.md "Non-finite values").  Finite values are those
 // of fmaxf up to the sign of a zero.  Running maxima, IoU terms and depth clamps keep fmaxf.

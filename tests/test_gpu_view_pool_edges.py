@@ -3,8 +3,8 @@ the visibility and softmax edges of tests/view_pool_edge_contract.py, and ``sgc_
 counts; tests/test_view_pool_edges_cpu.py runs the same checks on the oracle.
 
 Which kernel a parametrisation reaches (the dispatch at the end of view_pool.hip), g / d = view_group / view_depth:
-  view_mean    C 256 | 128: g1 d4 view_mean_group_kernel<64 | 32, 4>, g1 d1 <64 | 32, 1>, g0 view_mean_kernel;
-               C 32 view_mean_kernel; C 6 view_mean_scalar_kernel
+  view_mean    C 256 | 128: g1 d4 view_mean_group_kernel<64 | 32, 4>, g1 d1 <64 | 32, 1>, g0 view_mean_kernel<float4>;
+               C 32 view_mean_kernel<float4>; C 6 view_mean_kernel<float>
   view_attend  (C, heads) with heads * head_dim / 4 = 64: (256, 8 | 1 | 2 | 16), = 32: (128, 8 | 4):
                g1 d4 view_attend_group_kernel<64 | 32, 4>, g1 d1 <64 | 32, 1>, g0 view_attend_kernel<4>;
                C 64, 32 (8 heads) view_attend_kernel<4>; C 16, 8 view_attend_kernel<1>; C 24 raises

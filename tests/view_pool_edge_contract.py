@@ -30,7 +30,7 @@ PQ_DEPTHS = (4, 1, 2, 8)
 VARIANTS = ("production", "permuted")
 
 MEAN_GROUP_C = (256, 128)                              # reach view_mean_group_kernel
-MEAN_PLAIN_C = (32, 6)                                 # view_mean_kernel, view_mean_scalar_kernel
+MEAN_PLAIN_C = (32, 6)                                 # view_mean_kernel<float4>, view_mean_kernel<float>
 ATTEND_GROUP = ((256, 8), (128, 8), (256, 1), (256, 2), (256, 16), (128, 4))      # (C, heads): heads * G in {32, 64}
 ATTEND_PLAIN = ((64, 8), (32, 8), (16, 8), (8, 8))     # view_attend_kernel<4> (64, 32) and <1> (16, 8)
 PQ_C = (256, 128)
