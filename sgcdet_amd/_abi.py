@@ -8,8 +8,9 @@ points of ``include/sgcdet_amd_train.h`` have a table of their own
 asked for it (the product library; the oracle has no twin of them); the image-side
 convolutions of ``include/sgcdet_amd_image.h`` likewise (``IMAGE_SIGNATURES`` /
 ``IMAGE_INTROSPECTION``); ``include/sgcdet_amd_depth_train.h`` (``DEPTH_TRAIN_SIGNATURES`` /
-``DEPTH_TRAIN_INTROSPECTION``) and ``include/sgcdet_amd_level_train.h`` (``LEVEL_TRAIN_SIGNATURES`` /
-``LEVEL_TRAIN_INTROSPECTION``) are bound together with the training tables.  Nothing
+``DEPTH_TRAIN_INTROSPECTION``), ``include/sgcdet_amd_level_train.h`` (``LEVEL_TRAIN_SIGNATURES`` /
+``LEVEL_TRAIN_INTROSPECTION``) and ``include/sgcdet_amd_scene_batch.h`` (``SCENE_BATCH_SIGNATURES`` /
+``SCENE_BATCH_INTROSPECTION``) are bound together with the training tables.  Nothing
 here touches torch; pointers are plain integers (``tensor.data_ptr()``).
 """
 import ctypes as C
@@ -151,6 +152,18 @@ LEVEL_TRAIN_INTROSPECTION = {
     "sgc_layer_norm_rows_backward_workspace_floats": (C.c_int64, [_i] * 2),
 }
 
+# include/sgcdet_amd_scene_batch.h: the 3-D convolution passes on a batch of scenes in one launch (training on scene batches; bound
+# with the training tables).  With scenes = 1 they ARE sgc_conv3d_cl_bf16x3 / sgc_conv3d_wgrad_bf16x3, which call them.
+SCENE_BATCH_SIGNATURES = {
+    "sgc_conv3d_cl_bf16x3_batched": [_p] * 7 + [_i] * 10 + [_p, C.c_int64] + [_p],
+    "sgc_conv3d_wgrad_bf16x3_batched": [_p] * 3 + [_i] * 8 + [_p, C.c_int64] + [_p],
+}
+
+SCENE_BATCH_INTROSPECTION = {
+    "sgc_conv3d_batched_workspace_floats": (C.c_int64, [_i] * 10),
+    "sgc_conv3d_wgrad_batched_workspace_floats": (C.c_int64, [_i] * 8),
+}
+
 # include/sgcdet_amd_image.h: the 2-D convolutions of the image-side CNNs (no CPU-oracle twin)
 IMAGE_SIGNATURES = {
     "sgc_conv2d_nhwc_ex_bf16x3": [_p] * 7 + [_i] * 13 + [_p],
@@ -189,14 +202,17 @@ class Library:
 
     def __init__(self, path, train=False, image=False):
         """``train`` / ``image``: also bind (and require) the entry points of include/sgcdet_amd_train.h and
-        include/sgcdet_amd_depth_train.h, include/sgcdet_amd_level_train.h / of include/sgcdet_amd_image.h."""
+        include/sgcdet_amd_depth_train.h, include/sgcdet_amd_level_train.h, include/sgcdet_amd_scene_batch.h / of
+        include/sgcdet_amd_image.h."""
         self.path = str(path)
         self._dll = C.CDLL(self.path)
         missing = []
         signatures = {**SIGNATURES, **(TRAIN_SIGNATURES if train else {}), **(DEPTH_TRAIN_SIGNATURES if train else {}),
-                      **(LEVEL_TRAIN_SIGNATURES if train else {}), **(IMAGE_SIGNATURES if image else {})}
+                      **(LEVEL_TRAIN_SIGNATURES if train else {}), **(SCENE_BATCH_SIGNATURES if train else {}),
+                      **(IMAGE_SIGNATURES if image else {})}
         introspection = {**INTROSPECTION, **(TRAIN_INTROSPECTION if train else {}), **(DEPTH_TRAIN_INTROSPECTION if train else {}),
-                         **(LEVEL_TRAIN_INTROSPECTION if train else {}), **(IMAGE_INTROSPECTION if image else {})}
+                         **(LEVEL_TRAIN_INTROSPECTION if train else {}), **(SCENE_BATCH_INTROSPECTION if train else {}),
+                         **(IMAGE_INTROSPECTION if image else {})}
         for name, argtypes in signatures.items():
             try:
                 fn = getattr(self._dll, name)

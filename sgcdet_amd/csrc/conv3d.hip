@@ -5,6 +5,7 @@
 // gradients).  Here: the geometry, the plan, the split-K plumbing (zero fill, epilogue kernel) and the Winograd-z output transform.
 #include "conv_common.hpp"
 #include "tuning.hpp"
+#include "../../include/sgcdet_amd_scene_batch.h"
 
 namespace sgc {
 int g_conv_products = 3;     // NOT a tuning knob (it changes results; sgc_set_conv_products): the NP of csrc/mma.hpp -- 3 = fp32-faithful
@@ -195,6 +196,7 @@ using namespace sgc;
 static void conv_geometry(ConvParams &p, int ix, int iy, int iz, int Cin, int Cout, int ksize, int stride, int transposed,
                           int &ox, int &oy, int &oz) {
   p.Cin = Cin; p.Cout = Cout; p.ix = ix; p.iy = iy; p.iz = iz; p.transposed = transposed;
+  if (p.scenes < 1) p.scenes = 1;
   if (transposed) {
     p.gx = ix; p.gy = iy; p.gz = iz; p.ksize = 1; p.stride = 1; p.pad = 0; p.taps = 1;
     ox = 2 * ix; oy = 2 * iy; oz = 2 * iz;
@@ -275,7 +277,9 @@ static int conv_finish(const ConvParams &p, int64_t OV, hipStream_t st) {
   return check_launch("conv_epilogue_kernel");
 }
 
-// The plan of one bf16x3 call (p after conv_geometry; OV output rows; masked: the caller passes an output mask).  Pure: the
+// The plan of one bf16x3 call (p after conv_geometry; OV output rows of the launch, all scenes; masked: the caller passes an output
+// mask).  A scene batch keeps the family, the brick and the column tile of its per-scene grid (p.M, p.gx ..: a layer stays in its
+// numerical class whatever the batch); only the split count follows the workgroups of the whole launch.  Pure: the
 // knobs and the CU count are its only other inputs.  What the launch may still change is not planning: without a (large enough)
 // workspace a split launch accumulates with float atomics, and the 2-D forms, whose entry points carry none, take one split.
 static ConvPlan plan_conv(const ConvParams &p, int64_t OV, bool masked) {
@@ -286,8 +290,9 @@ static ConvPlan plan_conv(const ConvParams &p, int64_t OV, bool masked) {
   const bool narrow_32 = g_tune_halo_narrow >= 1 && g_tune_halo_narrow != 64 && p.Cout <= 32;   // 32-column tiles (8 x 1 waves) for the head's 28 columns
   const auto brick = [&pl](ConvFamily f, int bx, int by, int bz, int bn) { pl.family = f; pl.bx = bx; pl.by = by; pl.bz = bz; pl.bn = bn; };
   int small = 0;
-  if (!p.transposed && p.ksize == 1 && p.stride == 1 && !p.two_d && rows_gemm_supported(p.Cin, p.Cout, 0, 0, OV, p.Cin)) {
+  if (!p.transposed && p.ksize == 1 && p.stride == 1 && !p.two_d && rows_gemm_supported(p.Cin, p.Cout, 0, 0, OV / p.scenes, p.Cin)) {
     // 1x1x1 stride-1 layers are row GEMMs (the FFN of a level, TU/encoder.py:311-338): persistent weight-stationary kernel
+    // (asked with the rows of ONE scene: the family never depends on the batch)
     pl.family = kConvRowsGemm;
     return pl;
   } else if (halo && !p.two_d && p.M >= g_tune_halo_min_m) {
@@ -332,9 +337,9 @@ static ConvPlan plan_conv(const ConvParams &p, int64_t OV, bool masked) {
   if (pl.unsupported) return pl;
   if (pl.family == kConvTile) {
     pl.bn = p.Cout <= 64 ? 64 : 128;
-    pl.splitk = pick_split_steps(p, ceil_div(p.M, BM), ceil_div(p.Cout, pl.bn), g_tune_split_target, &pl.steps_per);
+    pl.splitk = pick_split_steps(p, ceil_div(p.M * p.scenes, BM), ceil_div(p.Cout, pl.bn), g_tune_split_target, &pl.steps_per);
   } else {
-    pl.splitk = halo_splitk(ceil_div(p.gx, pl.bx) * ceil_div(p.gy, pl.by) * ceil_div(p.gz, pl.bz), ceil_div(p.Cout, pl.bn), p.Cin / BK);
+    pl.splitk = halo_splitk(p.scenes * ceil_div(p.gx, pl.bx) * ceil_div(p.gy, pl.by) * ceil_div(p.gz, pl.bz), ceil_div(p.Cout, pl.bn), p.Cin / BK);
     // a Winograd stack of halo_min_m rows or more launches unsplit, as it always has (its per-layer A/B lines were taken that way, and
     // with scenes in flight a split only adds CU-time); the few-brick launches of the small stacks split like every halo launch
     if (pl.family == kConvHaloWZ && p.M >= g_tune_halo_min_m) pl.splitk = 1;
@@ -385,7 +390,7 @@ extern "C" int sgc_conv3d_cl_f32(const float *x, const float *wt, const float *s
 // the tile kernel addresses its input and its weights with 32-bit byte offsets into buffer descriptors
 static bool igemm_fits_32bit(const ConvParamsB &p) {
   const int64_t lim = 0xfffffff0ll - 65536;       // input: unsigned byte offsets; weights: the per-step offset is a signed scalar
-  return (int64_t)p.ix * p.iy * p.iz * p.Cin * 4 < lim && (int64_t)(p.transposed ? 8 : p.taps) * p.Cout * p.Cin * 2 < 0x7fffffffll;
+  return (int64_t)p.scenes * p.ix * p.iy * p.iz * p.Cin * 4 < lim && (int64_t)(p.transposed ? 8 : p.taps) * p.Cout * p.Cin * 2 < 0x7fffffffll;
 }
 
 // Same contract with the weights pre-split on the host: w_hi = bf16(w), w_lo = bf16(w - float(w_hi)),
@@ -395,8 +400,16 @@ static int conv3d_bf16x3(const float *x, const uint16_t *w_hi, const uint16_t *w
                          int ix, int iy, int iz, int Cin, int Cout, int ksize, int stride,
                          int transposed, int relu, float *workspace_or_null, int64_t workspace_floats,
                          const uint8_t *out_mask_or_null, sgc_stream_t stream, int two_d = 0,
-                         const float *act_scale = nullptr, int act_c0 = 0, int act_c1 = 0, int w_group_images = 0, int wz_Z = 0) {
+                         const float *act_scale = nullptr, int act_c0 = 0, int act_c1 = 0, int w_group_images = 0, int wz_Z = 0,
+                         int scenes = 1) {
+  if (scenes < 1) return set_error(SGC_EINVAL, "sgc_conv3d_cl_bf16x3_batched: scenes must be >= 1");
+  // the scene axis exists in the plain 3-D forms only
+  if (scenes > 1 && (out_mask_or_null || two_d || act_c1 > act_c0 || w_group_images || wz_Z))
+    return set_error(SGC_EUNSUP, "sgc_conv3d_cl_bf16x3_batched: no scene axis in the masked, activation, 2-D and Winograd forms");
+  if (scenes > 1 && ((int64_t)scenes * ix * iy * iz * 8 >= (1ll << 31) || scenes >= (1 << 15) || std::max(ix, std::max(iy, iz)) >= (1 << 15)))
+    return set_error(SGC_EUNSUP, "sgc_conv3d_cl_bf16x3_batched: too many rows (scenes * 8 * ix*iy*iz < 2^31, scenes and every extent < 2^15)");
   ConvParamsB p = {};
+  p.scenes = scenes;
   p.out_mask = out_mask_or_null;
   p.two_d = two_d;
   p.w_group_images = w_group_images;
@@ -409,10 +422,12 @@ static int conv3d_bf16x3(const float *x, const uint16_t *w_hi, const uint16_t *w
   p.scale = scale; p.shift = shift; p.residual = residual_or_null;
   p.ws = workspace_or_null; p.ws_floats = workspace_or_null ? workspace_floats : 0;
   if (!igemm_fits_32bit(p)) return set_error(SGC_EUNSUP, "sgc_conv3d_cl_bf16x3: the input must stay below 4 GiB and the weights below 2 GiB");
-  const int64_t OV = (int64_t)ox * oy * oz;
+  const int64_t OV = (int64_t)scenes * ox * oy * oz;         // output rows of the launch
   hipStream_t st = (hipStream_t)stream;
   const ConvPlan pl = plan_conv(p, OV, p.out_mask != nullptr);
   if (pl.unsupported) return set_error(SGC_EUNSUP, "%s", pl.unsupported);
+  if (pl.family == kConvRowsGemm && scenes > 1 && !rows_gemm_supported(Cin, Cout, 0, 0, OV, Cin))
+    return set_error(SGC_EUNSUP, "sgc_conv3d_cl_bf16x3_batched: the rows of the batch exceed the row GEMM's 4 GiB of x or y");
   if (pl.family == kConvRowsGemm)
     return rows_gemm_launch(x, Cin, w_hi, w_lo, scale, shift, residual_or_null, y, nullptr, (int)OV, Cin, Cout, relu, 0, 0, 0, st);
   p.splitk = pl.splitk; p.steps_per = pl.steps_per;
@@ -426,7 +441,7 @@ static int conv3d_bf16x3(const float *x, const uint16_t *w_hi, const uint16_t *w
   rc = conv_split_begin(p, OV, st);
   if (rc) return rc;
   if (pl.family == kConvTile) {
-    const dim3 grid(ceil_div(p.M, BM), ceil_div(Cout, pl.bn), (transposed ? 8 : 1) * p.splitk);
+    const dim3 grid(ceil_div(p.M * p.scenes, BM), ceil_div(Cout, pl.bn), (transposed ? 8 : 1) * p.splitk);
     const size_t smem = igemm_tile_lds_bytes(pl.bn);
     p.xcd_deal = (p.taps > 1 || transposed) && !p.two_d ? g_tune_igemm_xcd : 0;
     launch_igemm(p, pl.bn == 64, grid, smem, st);
@@ -438,13 +453,26 @@ static int conv3d_bf16x3(const float *x, const uint16_t *w_hi, const uint16_t *w
   return conv_finish(p, OV, st);
 }
 
+// A batch of `scenes` volumes of one grid in ONE launch: x [scenes * ix*iy*iz, Cin], scene s in rows [s * IV, (s + 1) * IV); y and
+// residual [scenes * OV, Cout]; weights, scale and shift shared.  Every scene is convolved on its own (zero padding at its border).
+// The family, brick and column tile are those of the per-scene grid; the split count follows the whole launch, so the result agrees
+// with per-scene launches to summation order (bitwise where the splits coincide).  scenes = 1 IS sgc_conv3d_cl_bf16x3.
+extern "C" int sgc_conv3d_cl_bf16x3_batched(const float *x, const uint16_t *w_hi, const uint16_t *w_lo, const float *scale,
+                                            const float *shift, const float *residual_or_null, float *y,
+                                            int ix, int iy, int iz, int Cin, int Cout, int ksize, int stride,
+                                            int transposed, int relu, int scenes, float *workspace_or_null, int64_t workspace_floats,
+                                            sgc_stream_t stream) {
+  return conv3d_bf16x3(x, w_hi, w_lo, scale, shift, residual_or_null, y, ix, iy, iz, Cin, Cout, ksize, stride, transposed, relu,
+                       workspace_or_null, workspace_floats, nullptr, stream, 0, nullptr, 0, 0, 0, 0, scenes);
+}
+
 extern "C" int sgc_conv3d_cl_bf16x3(const float *x, const uint16_t *w_hi, const uint16_t *w_lo, const float *scale,
                                     const float *shift, const float *residual_or_null, float *y,
                                     int ix, int iy, int iz, int Cin, int Cout, int ksize, int stride,
                                     int transposed, int relu, float *workspace_or_null, int64_t workspace_floats,
                                     sgc_stream_t stream) {
-  return conv3d_bf16x3(x, w_hi, w_lo, scale, shift, residual_or_null, y, ix, iy, iz, Cin, Cout, ksize, stride, transposed, relu,
-                       workspace_or_null, workspace_floats, nullptr, stream);
+  return sgc_conv3d_cl_bf16x3_batched(x, w_hi, w_lo, scale, shift, residual_or_null, y, ix, iy, iz, Cin, Cout, ksize, stride,
+                                      transposed, relu, 1, workspace_or_null, workspace_floats, stream);
 }
 
 // 2-D convolution over a stack of channels-last images (the producer side of the hand-over -- the FPN's
@@ -540,13 +568,14 @@ extern "C" int sgc_conv3d_winograd_z_bf16x3(const float *x, const uint16_t *wg_h
 // Split-K workspace (floats) the convolution above would use for a deterministic reduction; 0 = the layer is not
 // split.  The answer of the same dispatch as the launch: pick_splitk for sgc_conv3d_cl_f32 (bf16x3 = 0), plan_conv for
 // sgc_conv3d_cl_bf16x3 (bf16x3 = 1).
-extern "C" int64_t sgc_conv3d_workspace_floats(int ix, int iy, int iz, int Cin, int Cout, int ksize, int stride,
-                                               int transposed, int bf16x3) {
-  if (ix <= 0 || iy <= 0 || iz <= 0 || Cin <= 0 || Cout <= 0) return 0;
+extern "C" int64_t sgc_conv3d_batched_workspace_floats(int ix, int iy, int iz, int Cin, int Cout, int ksize, int stride,
+                                                       int transposed, int bf16x3, int scenes) {
+  if (ix <= 0 || iy <= 0 || iz <= 0 || Cin <= 0 || Cout <= 0 || scenes < 1 || (scenes > 1 && !bf16x3)) return 0;
   ConvParams p = {};
+  p.scenes = scenes;
   int ox, oy, oz;
   conv_geometry(p, ix, iy, iz, Cin, Cout, ksize, stride, transposed, ox, oy, oz);
-  const int64_t OV = (int64_t)ox * oy * oz;
+  const int64_t OV = (int64_t)scenes * ox * oy * oz;
   if (!bf16x3) {
     const int splitk = pick_splitk(p, ceil_div(p.M, BM), ceil_div(Cout, Cout <= 32 ? 32 : 128), g_tune_split_target);
     return splitk > 1 ? (int64_t)splitk * OV * Cout : 0;
@@ -555,6 +584,10 @@ extern "C" int64_t sgc_conv3d_workspace_floats(int ix, int iy, int iz, int Cin, 
   // a MASKED call on the whole-grid-brick grids takes the tile kernel (that brick carries no output mask): size for whichever
   // form splits further, so that neither ever falls back to float atomics for want of workspace
   return pl.family == kConvHaloGrid ? std::max(pl.ws_floats, plan_conv(p, OV, true).ws_floats) : pl.ws_floats;
+}
+extern "C" int64_t sgc_conv3d_workspace_floats(int ix, int iy, int iz, int Cin, int Cout, int ksize, int stride,
+                                               int transposed, int bf16x3) {
+  return sgc_conv3d_batched_workspace_floats(ix, iy, iz, Cin, Cout, ksize, stride, transposed, bf16x3, 1);
 }
 
 // y[rows, Cout] = x[rows, Cin] @ W^T + shift with the row count on the DEVICE: the pair-list stages size their
@@ -581,7 +614,7 @@ static int linear_rows(const float *x, const uint16_t *w_hi, const uint16_t *w_l
   p.y = y; p.shift = shift;
   p.Cin = Cin; p.Cout = Cout;
   p.ix = rows_cap; p.iy = 1; p.iz = 1; p.gx = rows_cap; p.gy = 1; p.gz = 1;
-  p.ksize = 1; p.stride = 1; p.pad = 0; p.taps = 1; p.splitk = 1; p.M = rows_cap; p.m_dev = rows_dev_or_null;
+  p.ksize = 1; p.stride = 1; p.pad = 0; p.taps = 1; p.splitk = 1; p.M = rows_cap; p.scenes = 1; p.m_dev = rows_dev_or_null;
   p.hm_S = hm_S; p.hm_cm = hm_cm; p.hm_bf16 = hm_bf16;
   const bool narrow = Cout <= 64;
   const int bn = narrow ? 64 : 128;

@@ -62,9 +62,12 @@ __host__ __device__ constexpr size_t halo_tab_offset(int lrows, int mrows = 256,
 // fragments, refilled tile by tile behind the last MFMA that reads each.  What differs: the LDS rows are 96 bytes (halo_pitch), the
 // lane -> voxel table deals rows by residue mod 8, the weight rows a thread stages, the fragment reads, the product loop and the
 // accumulator -> LDS-tile store of the epilogue.  The instruction sums differently: last-bit differences against MF = 32.
-template <int BX, int BY, int BZ, int BNV = 128, int NP = 3, bool TD = false, bool STG = true, bool WZ = false, int MF = 32>
+// SC: the launch holds a batch of scenes (p.scenes > 1, sgc_conv3d_cl_bf16x3_batched; 3-D forms only).  An instantiation of its own:
+// the scene-less kernel -- the one inference runs -- is the code it always was, only a batch pays for the scene decode.
+template <int BX, int BY, int BZ, int BNV = 128, int NP = 3, bool TD = false, bool STG = true, bool WZ = false, int MF = 32, bool SC = false>
 __global__ __launch_bounds__(512) void conv3d_halo_bf16x3_kernel(const ConvParamsB p) {
   static_assert(!WZ || TD, "the virtual Winograd stack is a 2-D form");
+  static_assert(!SC || (!TD && !WZ), "the scene axis exists in the 3-D forms only");
   static_assert(MF == 32 || (MF == 16 && WZ && STG && BNV == 128 && BX * BY * BZ <= 256), "the 16x16x32 form: pipelined Winograd bricks only");
   constexpr int LDKH = halo_ldk(MF);                    // bf16 per LDS row (shadows the 80-byte rows of conv_common.hpp)
   constexpr int NTAP = TD ? 9 : 27, XO = TD ? 0 : 1;    // taps; halo width along x
@@ -92,7 +95,16 @@ __global__ __launch_bounds__(512) void conv3d_halo_bf16x3_kernel(const ConvParam
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid / WNV, wn = wid % WNV;
   const int nby = (p.gy + BY - 1) / BY, nbz = (p.gz + BZ - 1) / BZ;
+  // scene of this workgroup (sgc_conv3d_cl_bf16x3_batched launches scenes * bricks of them): its rows start at in0 / orow0, the
+  // halo test below is against the scene's own grid, so rows of a neighbouring scene are never staged
   int bid = blockIdx.x;
+  int in0 = 0;
+  if constexpr (SC) {
+    const int per_scene = ((p.gx + BX - 1) / BX) * nby * nbz;
+    const int scene = bid / per_scene;
+    bid -= scene * per_scene;
+    in0 = scene * (p.ix * p.iy * p.iz);
+  }
   const int bk = bid % nbz; bid /= nbz;
   const int bj = bid % nby; const int bi = bid / nby;
   const int X0 = bi * BX, Y0 = bj * BY, Z0 = bk * BZ;
@@ -186,7 +198,7 @@ __global__ __launch_bounds__(512) void conv3d_halo_bf16x3_kernel(const ConvParam
         if (col >= p.Cout) continue;
         const int x = X0 + rl / (BY * BZ), y = Y0 + (rl / BZ) % BY, z = Z0 + rl % BZ;
         if (x >= p.gx || y >= p.gy || z >= p.gz) continue;
-        const int64_t orow = ((int64_t)x * p.gy + y) * p.gz + z;
+        const int64_t orow = ((int64_t)x * p.gy + y) * p.gz + z;       // (the masked form is one scene)
         for (int q = 0; q < 4 && col + q < p.Cout; ++q) {
           float v = 0.f;
           if (p.splitk > 1) { p.ws[(int64_t)blockIdx.z * p.ws_stride + orow * p.Cout + col + q] = 0.f; continue; }
@@ -232,7 +244,7 @@ __global__ __launch_bounds__(512) void conv3d_halo_bf16x3_kernel(const ConvParam
   // a slice / a tap then only moves a uniform offset.  Buffer loads return zeros past the tensor, so the loads carry no branch.
   constexpr unsigned OOB = 0xfffffff0u;
   const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float *>(p.x), 0, (int)(unsigned)((int64_t)(WZ ? p.wz_Z : p.ix) * p.iy * p.iz * p.Cin * 4), 0x00020000);
+      const_cast<float *>(p.x), 0, (int)(unsigned)((int64_t)(WZ ? p.wz_Z : SC ? p.scenes * p.ix : p.ix) * p.iy * p.iz * p.Cin * 4), 0x00020000);
   const int w_bytes = (int)(unsigned)((int64_t)NTAP * p.Cout * p.Cin * 2);
   // weight set of this brick: one for the whole launch, or -- 2-D form with image groups -- that of the group its images belong to
   const int64_t w_set = (TD && p.w_group_images > 0) ? (int64_t)(X0 / p.w_group_images) * NTAP * p.Cout * p.Cin : 0;
@@ -255,7 +267,7 @@ __global__ __launch_bounds__(512) void conv3d_halo_bf16x3_kernel(const ConvParam
       aoff[i] = in && za >= 0 ? ((col + (unsigned)za) * (unsigned)p.Cin + c4 * 4) * 4u : OOB;
       aoffb[i] = in && zb < p.wz_Z ? ((col + (unsigned)zb) * (unsigned)p.Cin + c4 * 4) * 4u : OOB;
     } else {
-      aoff[i] = in ? ((unsigned)((gx * p.iy + gy) * p.iz + gz) * (unsigned)p.Cin + c4 * 4) * 4u : OOB;
+      aoff[i] = in ? ((unsigned)((SC ? in0 : 0) + (gx * p.iy + gy) * p.iz + gz) * (unsigned)p.Cin + c4 * 4) * 4u : OOB;
     }
   }
   const float wz_sign = WZ && (X0 / max(p.wz_Z >> 1, 1)) == 1 ? 1.f : -1.f;      // t1 = d1 + d2; t0, t2, t3 are differences
@@ -542,6 +554,14 @@ __global__ __launch_bounds__(512) void conv3d_halo_bf16x3_kernel(const ConvParam
   SGC_HALO_STAMP(2);
   if constexpr ((SGC_HALO_SKIP & 128) != 0) { if (p.relu != 77) return; }     // timing builds: no epilogue (the condition keeps the MFMAs alive)
 
+  // first output row of this workgroup's scene: derived from the workgroup id again HERE (the empty asm keeps the compiler from
+  // carrying the value of the prologue through the tap loop, where every register counts)
+  int64_t orow0 = 0;
+  if constexpr (SC) {
+    int bid_e = blockIdx.x;
+    asm volatile("" : "+s"(bid_e));
+    orow0 = (int64_t)(bid_e / (((p.gx + BX - 1) / BX) * ((p.gy + BY - 1) / BY) * ((p.gz + BZ - 1) / BZ))) * p.gx * p.gy * p.gz;
+  }
   // Epilogue through LDS (as in the implicit-GEMM kernel): the halo / weight buffers are free, the 256 x 128 tile
   // leaves as 16-byte row-contiguous stores instead of 64 four-byte stores per lane.
   if ((p.Cout & 3) == 0 && (p.splitk == 1 || p.ws)) {
@@ -576,7 +596,7 @@ __global__ __launch_bounds__(512) void conv3d_halo_bf16x3_kernel(const ConvParam
       if (r & kPadRow) continue;
       const int x = X0 + r / (BY * BZ), y = Y0 + (r / BZ) % BY, z = Z0 + r % BZ;
       if (x >= p.gx || y >= p.gy || z >= p.gz) continue;
-      const int64_t orow = ((int64_t)x * p.gy + y) * p.gz + z;
+      const int64_t orow = (SC ? orow0 : 0) + ((int64_t)x * p.gy + y) * p.gz + z;
       float4 v = *reinterpret_cast<const float4 *>(cs + rl * LDC + c4 * 4);
       if (p.splitk > 1) {
         *reinterpret_cast<float4 *>(p.ws + (int64_t)blockIdx.z * p.ws_stride + orow * p.Cout + col) = v;
@@ -607,7 +627,7 @@ __global__ __launch_bounds__(512) void conv3d_halo_bf16x3_kernel(const ConvParam
     const int r = vox_tab[tab_row];
     const int x = X0 + r / (BY * BZ), y = Y0 + (r / BZ) % BY, z = Z0 + r % BZ;
     if ((r & kPadRow) || x >= p.gx || y >= p.gy || z >= p.gz) return;
-    const int64_t orow = ((int64_t)x * p.gy + y) * p.gz + z;
+    const int64_t orow = (SC ? orow0 : 0) + ((int64_t)x * p.gy + y) * p.gz + z;
     float *dst = p.y + orow * p.Cout + col;
     if (p.splitk > 1) {
       if (p.ws) p.ws[(int64_t)blockIdx.z * p.ws_stride + orow * p.Cout + col] = a;
@@ -645,7 +665,7 @@ __global__ __launch_bounds__(512) void conv3d_halo_bf16x3_kernel(const ConvParam
         const int r = vox_tab[(wm * RT + i) * 32 + (k & 3) + 8 * (k >> 2) + 4 * (lane >> 5)];
         const int x = X0 + r / (BY * BZ), y = Y0 + (r / BZ) % BY, z = Z0 + r % BZ;
         if ((r & kPadRow) || x >= p.gx || y >= p.gy || z >= p.gz) continue;
-        const int64_t orow = ((int64_t)x * p.gy + y) * p.gz + z;
+        const int64_t orow = (SC ? orow0 : 0) + ((int64_t)x * p.gy + y) * p.gz + z;
         float *dst = p.y + orow * p.Cout + col;
         if (p.splitk > 1) {
           if (p.ws) p.ws[(int64_t)blockIdx.z * p.ws_stride + orow * p.Cout + col] = acc[i][j][k];
@@ -674,8 +694,11 @@ __global__ __launch_bounds__(512) void conv3d_halo_bf16x3_kernel(const ConvParam
 // 155.8 vs 151.8 on 512 -> 512 @ 20x20x8 (profiles/r06_wz_skip.txt: the 13 us the restaging costs are not vector-issue time).
 
 // one launch of the form a plan names; p.splitk is the caller's (plan_conv and the launch-time downgrades of conv3d_bf16x3)
-template <int BX, int BY, int BZ, int BNV, int NP, bool TD, bool STG, bool WZ = false, int MF = 32>
+template <int BX, int BY, int BZ, int BNV, int NP, bool TD, bool STG, bool WZ = false, int MF = 32, bool SC = false>
 static int launch_halo_k(ConvParamsB &p, hipStream_t st) {
+  if constexpr (!SC && !TD && !WZ) {                    // a batch of volumes: the instantiation with the scene decode
+    if (p.scenes > 1) return launch_halo_k<BX, BY, BZ, BNV, NP, TD, STG, WZ, MF, true>(p, st);
+  }
 #if defined(SGC_HALO_STAMPS)
   p.stamps = g_halo_stamp_buf;
 #endif
@@ -685,10 +708,10 @@ static int launch_halo_k(ConvParamsB &p, hipStream_t st) {
   const size_t smem = halo_tab_offset(LROWS, MROWS, MROWS > 256 ? BNV : 128, halo_ldk(MF)) + (MROWS + 256) * sizeof(uint16_t);   // table + 8 x 32 scratch
   static_assert(halo_tab_offset(LROWS, MROWS, MROWS > 256 ? BNV : 128, halo_ldk(MF)) + (MROWS + 256) * sizeof(uint16_t) <= 160 * 1024, "brick does not fit the LDS");
   static std::atomic<uint64_t> attr_done{0};
-  ensure_dynamic_lds((const void *)conv3d_halo_bf16x3_kernel<BX, BY, BZ, BNV, NP, TD, STG, WZ, MF>, (int)smem, attr_done);
-  const int bricks = ceil_div(p.gx, BX) * ceil_div(p.gy, BY) * ceil_div(p.gz, BZ);
+  ensure_dynamic_lds((const void *)conv3d_halo_bf16x3_kernel<BX, BY, BZ, BNV, NP, TD, STG, WZ, MF, SC>, (int)smem, attr_done);
+  const int bricks = (SC ? p.scenes : 1) * ceil_div(p.gx, BX) * ceil_div(p.gy, BY) * ceil_div(p.gz, BZ);
   const int nb = ceil_div(p.Cout, BNV);
-  hipLaunchKernelGGL((conv3d_halo_bf16x3_kernel<BX, BY, BZ, BNV, NP, TD, STG, WZ, MF>), dim3(bricks, nb, p.splitk), dim3(512), smem, st, p);
+  hipLaunchKernelGGL((conv3d_halo_bf16x3_kernel<BX, BY, BZ, BNV, NP, TD, STG, WZ, MF, SC>), dim3(bricks, nb, p.splitk), dim3(512), smem, st, p);
   return check_launch("conv3d_halo_bf16x3_kernel");
 }
 

@@ -186,7 +186,9 @@ __global__ __launch_bounds__(256) void conv3d_igemm_f32_kernel(const ConvParams 
 // ---------------------------------------------------------------------------------------------
 // NP: bf16 products per multiply-add (3 = fp32-faithful split, 1 = hi * hi only).  The tile itself -- LDS plan, staging deal, K loop,
 // MFMA group, C scatter -- is IgemmTile (igemm_tile.hpp); here are the addressing of volumes and the store paths.
-template <int BN, int WM, int WN, int NP = 3>
+// SC: the launch holds a batch of scenes (p.scenes > 1, sgc_conv3d_cl_bf16x3_batched).  An instantiation of its own, so that the
+// scene-less kernel is the code it always was -- same registers, same spills -- and only a batch pays for the scene decode.
+template <int BN, int WM, int WN, int NP = 3, bool SC = false>
 __global__ __launch_bounds__(WM * WN * 64) void conv3d_igemm_bf16x3_kernel(const ConvParamsB p) {
   using Tile = IgemmTile<BN, WM, WN, NP>;
   constexpr int NT = Tile::NT, TM = Tile::TM, TN = Tile::TN, ACH = Tile::ACH;
@@ -205,7 +207,8 @@ __global__ __launch_bounds__(WM * WN * 64) void conv3d_igemm_bf16x3_kernel(const
   const int m0 = bx * BM, n0 = by * BN;
   if (p.zero_row && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0)
     for (int c = threadIdx.x; c < p.Cout; c += NT) p.zero_row[c] = 0.f;
-  const int Mrows = p.m_dev ? min(p.M, *p.m_dev) : p.M;
+  const int Mall = SC ? p.M * p.scenes : p.M;            // GEMM rows of the launch: scene s owns [s * M, (s + 1) * M)
+  const int Mrows = p.m_dev ? min(Mall, *p.m_dev) : Mall;
   if (m0 >= Mrows) return;
   int zid = bz;
   int parity = 0;
@@ -225,18 +228,24 @@ __global__ __launch_bounds__(WM * WN * 64) void conv3d_igemm_bf16x3_kernel(const
   // scalar divisions of the tap decode, on 12 MFMAs per wave).
   Tile t(smem_b, threadIdx.x);
   const int tid = t.tid, lane = t.lane, wm = t.wm, wn = t.wn;
+  // a tile of 128 rows may span scenes (400 rows per scene at the coarsest scale): the scene is decoded per row and the neighbour
+  // test below is against that scene's grid.  A batch (SC) keeps the scene in the upper half of ax[] (the host checks every
+  // extent of the grid and the scene count < 2^15): no register per chunk beyond the scene-less kernel's, unpacked once per TAP
   int ax[ACH], ay[ACH], az[ACH];
   bool arow_ok[ACH];
+  const int IV = p.ix * p.iy * p.iz;
+  constexpr bool batch = SC;
 #pragma unroll
   for (int i = 0; i < ACH; ++i) {
     const int m = m0 + t.a_row(i);
     arow_ok[i] = m < Mrows;
-    const int mm = arow_ok[i] ? m : 0;
+    const int mg = arow_ok[i] ? m : 0, sc = batch ? mg / p.M : 0;
+    const int mm = mg - sc * p.M;
     az[i] = mm % p.gz;
     ay[i] = (mm / p.gz) % p.gy;
-    ax[i] = mm / (p.gz * p.gy);
+    ax[i] = mm / (p.gz * p.gy) + (sc << 16);
   }
-  t.bind(p.x, (int64_t)p.ix * p.iy * p.iz * p.Cin * 4, p.w_hi, p.w_lo, (int64_t)(p.transposed ? 8 : p.taps) * p.Cout * p.Cin * 2,
+  t.bind(p.x, (int64_t)(SC ? p.scenes : 1) * IV * p.Cin * 4, p.w_hi, p.w_lo, (int64_t)(p.transposed ? 8 : p.taps) * p.Cout * p.Cin * 2,
          n0, p.Cout, p.Cin);
   auto set_tap = [&](int tap) {
     int dx = 0, dy = 0, dz = 0;
@@ -246,10 +255,13 @@ __global__ __launch_bounds__(WM * WN * 64) void conv3d_igemm_bf16x3_kernel(const
     }
 #pragma unroll
     for (int i = 0; i < ACH; ++i) {
-      const int xx = ax[i] * p.stride + dx - p.pad, yy = ay[i] * p.stride + dy - p.pad,
+      int axp = ax[i];
+      if constexpr (SC) asm volatile("" : "+v"(axp));     // unpacked per tap: hoisted out of the K loop the scene's base costs a register per chunk
+      const int sc = batch ? axp >> 16 : 0, axl = batch ? axp & 0xffff : axp;
+      const int xx = axl * p.stride + dx - p.pad, yy = ay[i] * p.stride + dy - p.pad,
                 zz = az[i] * p.stride + dz - p.pad;
       const bool ok = arow_ok[i] && xx >= 0 && xx < p.ix && yy >= 0 && yy < p.iy && zz >= 0 && zz < p.iz;
-      t.aoff[i] = ok ? ((unsigned)((xx * p.iy + yy) * p.iz + zz) * (unsigned)p.Cin + t.c4 * 4) * 4u : Tile::OOB;
+      t.aoff[i] = ok ? ((unsigned)(sc * IV + (xx * p.iy + yy) * p.iz + zz) * (unsigned)p.Cin + t.c4 * 4) * 4u : Tile::OOB;
     }
   };
   if constexpr ((SGC_TILE_SKIP & 6) != 0) {               // timing builds: the registers the skipped loads would have filled
@@ -273,10 +285,11 @@ __global__ __launch_bounds__(WM * WN * 64) void conv3d_igemm_bf16x3_kernel(const
   if constexpr ((SGC_TILE_SKIP & 64) != 0) { if (p.relu != 77) return; }      // timing builds: no epilogue
 
   auto out_row = [&](int m) -> int64_t {                  // transposed: GEMM row (input voxel) -> output voxel of this parity
-    if (!p.transposed) return m;
-    const int z = m % p.gz, y = (m / p.gz) % p.gy, x = m / (p.gz * p.gy);
+    if (!p.transposed) return m;                          // (the output grid is the row grid: scene s starts at row s * M)
+    const int sc = SC ? m / p.M : 0, ml = m - sc * p.M;
+    const int z = ml % p.gz, y = (ml / p.gz) % p.gy, x = ml / (p.gz * p.gy);
     const int px = parity >> 2, py = (parity >> 1) & 1, pz = parity & 1;
-    return ((int64_t)(2 * x + px) * (2 * p.gy) + (2 * y + py)) * (2 * p.gz) + (2 * z + pz);
+    return (int64_t)sc * 8 * p.M + ((int64_t)(2 * x + px) * (2 * p.gy) + (2 * y + py)) * (2 * p.gz) + (2 * z + pz);
   };
   // Store paths.  Whole float4 columns and no atomics: through LDS (the partial tiles of a split reduction, the residual and
   // the scale / shift vectors move 16 bytes at a time too).
@@ -368,17 +381,20 @@ int launch_igemm_f32(const ConvParams &p, bool narrow, dim3 grid, hipStream_t st
 }
 
 // one launch of the tile-per-workgroup implicit-GEMM kernel in the arithmetic mode of g_conv_products
-template <int NP>
+template <int NP, bool SC>
 static void launch_igemm_np(const ConvParamsB &p, bool narrow, dim3 grid, size_t smem, hipStream_t st) {
   static std::atomic<uint64_t> done[2];
   constexpr int big = igemm_tile_lds_bytes(128);
-  ensure_dynamic_lds((const void *)conv3d_igemm_bf16x3_kernel<128, 2, 2, NP>, big, done[0]);
-  ensure_dynamic_lds((const void *)conv3d_igemm_bf16x3_kernel<128, 4, 2, NP>, big, done[1]);
-  if (narrow) hipLaunchKernelGGL((conv3d_igemm_bf16x3_kernel<64, 4, 1, NP>), grid, dim3(256), smem, st, p);
-  else if (g_tune_conv_waves == 8) hipLaunchKernelGGL((conv3d_igemm_bf16x3_kernel<128, 4, 2, NP>), grid, dim3(512), smem, st, p);
-  else hipLaunchKernelGGL((conv3d_igemm_bf16x3_kernel<128, 2, 2, NP>), grid, dim3(256), smem, st, p);
+  ensure_dynamic_lds((const void *)conv3d_igemm_bf16x3_kernel<128, 2, 2, NP, SC>, big, done[0]);
+  ensure_dynamic_lds((const void *)conv3d_igemm_bf16x3_kernel<128, 4, 2, NP, SC>, big, done[1]);
+  if (narrow) hipLaunchKernelGGL((conv3d_igemm_bf16x3_kernel<64, 4, 1, NP, SC>), grid, dim3(256), smem, st, p);
+  else if (g_tune_conv_waves == 8) hipLaunchKernelGGL((conv3d_igemm_bf16x3_kernel<128, 4, 2, NP, SC>), grid, dim3(512), smem, st, p);
+  else hipLaunchKernelGGL((conv3d_igemm_bf16x3_kernel<128, 2, 2, NP, SC>), grid, dim3(256), smem, st, p);
 }
 void launch_igemm(const ConvParamsB &p, bool narrow, dim3 grid, size_t smem, hipStream_t st) {
-  with_products(g_conv_products, [&](auto np) { launch_igemm_np<np()>(p, narrow, grid, smem, st); });
+  with_products(g_conv_products, [&](auto np) {
+    if (p.scenes > 1) launch_igemm_np<np(), true>(p, narrow, grid, smem, st);
+    else launch_igemm_np<np(), false>(p, narrow, grid, smem, st);
+  });
 }
 }  // namespace sgc

@@ -2,6 +2,7 @@
 // halo forms of the 3-D entry, their reduction and the entry points.
 #include "conv_common.hpp"
 #include "mma.hpp"
+#include "../../include/sgcdet_amd_scene_batch.h"
 #include "diag.hpp"
 #include "tuning.hpp"
 
@@ -24,8 +25,9 @@ struct WgradParams {
   int Cin, Cout;
   int ix, iy, iz, ox, oy, oz;
   int ksize, stride, pad, taps;
-  int OV, ksteps, splits, steps_per_split;
-  int ax, by, cz;           // 32 = ax * (oy * oz) + by * oz + cz: the per-step advance of a voxel's (x, y, z) (see load_step)
+  int OV, ksteps, splits, steps_per_split;     // OV: reduction rows of the launch = scenes * ox * oy * oz
+  int scenes;               // volumes of one grid behind x and dy (sgc_conv3d_wgrad_bf16x3_batched): the scene axis is more reduction rows
+  int as, ax, by, cz;       // 32 = as * (ox * oy * oz) + ax * (oy * oz) + by * oz + cz: the per-step advance of a voxel's (scene, x, y, z)
 };
 
 // WM = 2: 4 waves (2 x 2, 64 x 64 each), every thread stages one block of BOTH operands; WM = 4: 8 waves (4 x 2, 32 x 64 each),
@@ -34,7 +36,9 @@ struct WgradParams {
 // IMG: the 2-D form (sgc_conv2d_wgrad_bf16x3).  A reduction row decodes as (image, h, w) = (x, y, z) of the carried coordinates,
 // the taps are the k * k taps of (y, z) only and the leading coordinate is neither strided nor padded -- it picks the image, so
 // no tap crosses one.  Staging, MMA and store are the 3-D kernel's.
-template <int WM, bool IMG = false>
+// SC: x and dy hold a batch of scenes (p.scenes > 1): the carried coordinates get a scene digit.  An instantiation of its own: the
+// scene-less kernel is the code it always was.
+template <int WM, bool IMG = false, bool SC = false>
 __global__ __launch_bounds__(WM * 128) void conv3d_wgrad_bf16x3_kernel(const WgradParams p) {
   constexpr int TMW = 4 / WM * 1;                           // 32-row tiles per wave along M: 2 (WM = 2) or 1 (WM = 4)
   constexpr int BMW = 128, BNW = 128;
@@ -61,12 +65,15 @@ __global__ __launch_bounds__(WM * 128) void conv3d_wgrad_bf16x3_kernel(const Wgr
   const __amdgpu_buffer_rsrc_t dyr = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float *>(p.dy), 0, (int)(unsigned)((int64_t)p.OV * p.Cout * 4), 0x00020000);
   const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float *>(p.x), 0, (int)(unsigned)((int64_t)p.ix * p.iy * p.iz * p.Cin * 4), 0x00020000);
-  int vx[4], vy[4], vz[4];
+      const_cast<float *>(p.x), 0, (int)(unsigned)((int64_t)(SC ? p.scenes : 1) * p.ix * p.iy * p.iz * p.Cin * 4), 0x00020000);
+  int vs[SC ? 4 : 1], vx[4], vy[4], vz[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const int o = s_lo * 32 + 4 * kb + j;                   // may be >= OV: the coordinates then run past ox and the loads are OOB
-    vz[j] = o % p.oz; vy[j] = (o / p.oz) % p.oy; vx[j] = o / (p.oz * p.oy);
+    const int o = s_lo * 32 + 4 * kb + j;                   // may be >= OV: `live` below is false then and the loads are OOB
+    vz[j] = o % p.oz; vy[j] = (o / p.oz) % p.oy;
+    const int xs = o / (p.oz * p.oy);
+    if constexpr (SC) { vs[j] = xs / p.ox; vx[j] = xs - vs[j] * p.ox; }
+    else vx[j] = xs;                                        // (one scene: the coordinates run past ox and the loads are OOB)
   }
   int o_base = s_lo * 32 + 4 * kb;
   auto load_step = [&]() {                                  // loads the step the carried coordinates stand at, then advances them
@@ -82,20 +89,25 @@ __global__ __launch_bounds__(WM * 128) void conv3d_wgrad_bf16x3_kernel(const Wgr
         const int xx = IMG ? vx[j] : vx[j] * p.stride + dx - p.pad, yy = vy[j] * p.stride + dy_ - p.pad, zz = vz[j] * p.stride + dz - p.pad;
         const bool in = live && b_ok && xx >= 0 && xx < p.ix && yy >= 0 && yy < p.iy && zz >= 0 && zz < p.iz;
         const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(
-            xr, in ? ((unsigned)((xx * p.iy + yy) * p.iz + zz) * (unsigned)p.Cin + ci0 + 4 * cb) * 4u : OOB, 0, 0);
+            xr, in ? ((unsigned)((((SC ? vs[SC ? j : 0] * p.ix : 0) + xx) * p.iy + yy) * p.iz + zz) * (unsigned)p.Cin + ci0 + 4 * cb) * 4u : OOB, 0, 0);
         rb[j] = make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
       }
     }
     if (role != 0) {                                        // carry the coordinates to the next step: selects only, no branch
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        vz[j] += p.cz;                                      // 32 = ax * (oy * oz) + by * oz + cz: one carry per digit, always exact
+        vz[j] += p.cz;                                      // 32 = as * OV1 + ax * (oy * oz) + by * oz + cz: one carry per digit, always exact
         const int c1 = vz[j] >= p.oz ? 1 : 0;
         vz[j] -= c1 ? p.oz : 0;
         vy[j] += p.by + c1;
         const int c2 = vy[j] >= p.oy ? 1 : 0;
         vy[j] -= c2 ? p.oy : 0;
         vx[j] += p.ax + c2;
+        if constexpr (SC) {
+          const int c3 = vx[j] >= p.ox ? 1 : 0;             // past the scene's last voxel: the next scene's first (its rows follow in x and dy)
+          vx[j] -= c3 ? p.ox : 0;
+          vs[j] += p.as + c3;
+        }
       }
     }
     o_base += 32;
@@ -201,7 +213,8 @@ struct WgradHaloParams {
   float *out;               // dW [27][Cout][Cin] (one split) or the workspace [splits][27][Cout][Cin]
   int Cin, Cout;
   int gx, gy, gz;           // grid (input = output grid: stride 1, padding 1)
-  int nbricks, bricks_per_split;
+  int nbricks, bricks_per_split;   // nbricks = scenes * bricks_per_scene: brick b belongs to scene b / bricks_per_scene
+  int scenes, bricks_per_scene;
 };
 
 typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
@@ -236,9 +249,9 @@ __global__ __launch_bounds__(64 * NW) void conv3d_wgrad_halo_kernel(const WgradH
   const int nby = (p.gy + BY - 1) / BY, nbz = (p.gz + BZ - 1) / BZ;
   constexpr unsigned OOB = 0xfffffff0u;
   const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float *>(p.x), 0, (int)(unsigned)((int64_t)p.gx * p.gy * p.gz * p.Cin * 4), 0x00020000);
+      const_cast<float *>(p.x), 0, (int)(unsigned)((int64_t)p.scenes * p.gx * p.gy * p.gz * p.Cin * 4), 0x00020000);
   const __amdgpu_buffer_rsrc_t dr = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float *>(p.dy), 0, (int)(unsigned)((int64_t)p.gx * p.gy * p.gz * p.Cout * 4), 0x00020000);
+      const_cast<float *>(p.dy), 0, (int)(unsigned)((int64_t)p.scenes * p.gx * p.gy * p.gz * p.Cout * 4), 0x00020000);
   // staging assignment: the x halo goes slab by slab (hx = 0 .. 9; a slab is 60 rows (hy, hz) x 8 float4, APASS passes of
   // RPP rows), dy voxel-row by voxel-row: the x index of every global load is wave-uniform, (y, z) are per-thread constants
   constexpr int APASS = 512 / NT, RPP = HY * HZ / APASS, NA = (BX + 2) * APASS;
@@ -246,7 +259,8 @@ __global__ __launch_bounds__(64 * NW) void conv3d_wgrad_halo_kernel(const WgradH
   const int a_r = tid >> 3, a_c4 = tid & 7;
   const int d_r = tid / DCH, d_c4 = tid % DCH;
   float4 ra[NA], rd[ND];
-  auto load_brick = [&](int b) {
+  auto load_brick = [&](int bg) {
+    const int sc = bg / p.bricks_per_scene, b = bg - sc * p.bricks_per_scene, xs0 = sc * p.gx;     // the scene's first x slab in x and dy
     const int bk = b % nbz, bj = (b / nbz) % nby, bi = b / (nbz * nby);
     const int X0 = bi * BX, Y0 = bj * BY, Z0 = bk * BZ;
 #pragma unroll
@@ -258,7 +272,7 @@ __global__ __launch_bounds__(64 * NW) void conv3d_wgrad_halo_kernel(const WgradH
       for (int i = 0; i < BX + 2; ++i) {
         const int x = X0 + i - 1;                                                       // uniform
         const bool xin = x >= 0 && x < p.gx;
-        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(xr, xin ? voff : OOB, xin ? (int)((unsigned)x * (unsigned)(p.gy * p.gz) * (unsigned)p.Cin * 4u) : 0, 0);
+        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(xr, xin ? voff : OOB, xin ? (int)((unsigned)(xs0 + x) * (unsigned)(p.gy * p.gz) * (unsigned)p.Cin * 4u) : 0, 0);
         ra[i * APASS + j] = make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
       }
     }
@@ -268,7 +282,7 @@ __global__ __launch_bounds__(64 * NW) void conv3d_wgrad_halo_kernel(const WgradH
       const int x = X0 + vx / (BY * BZ), y = Y0 + r / BZ, z = Z0 + r % BZ;
       const bool xin = x < p.gx, in = y < p.gy && z < p.gz;
       const unsigned voff = in && xin ? ((unsigned)(y * p.gz + z) * (unsigned)p.Cout + co0 + d_c4 * 4) * 4u : OOB;
-      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(dr, voff, xin ? (int)((unsigned)x * (unsigned)(p.gy * p.gz) * (unsigned)p.Cout * 4u) : 0, 0);
+      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(dr, voff, xin ? (int)((unsigned)(xs0 + x) * (unsigned)(p.gy * p.gz) * (unsigned)p.Cout * 4u) : 0, 0);
       rd[i] = make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
     }
   };
@@ -422,9 +436,9 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_halo2_kernel(const WgradHalo
   const int nby = (p.gy + BY - 1) / BY, nbz = (p.gz + BZ - 1) / BZ;
   constexpr unsigned OOB = 0xfffffff0u;
   const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float *>(p.x), 0, (int)(unsigned)((int64_t)p.gx * p.gy * p.gz * p.Cin * 4), 0x00020000);
+      const_cast<float *>(p.x), 0, (int)(unsigned)((int64_t)p.scenes * p.gx * p.gy * p.gz * p.Cin * 4), 0x00020000);
   const __amdgpu_buffer_rsrc_t dr = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float *>(p.dy), 0, (int)(unsigned)((int64_t)p.gx * p.gy * p.gz * p.Cout * 4), 0x00020000);
+      const_cast<float *>(p.dy), 0, (int)(unsigned)((int64_t)p.scenes * p.gx * p.gy * p.gz * p.Cout * 4), 0x00020000);
   // staging: x halo slab by slab (hx = 0 .. 5; 60 rows x 8 float4 in two passes of 30 rows), dy in passes of DROWS voxels
   constexpr int RPP = HY * HZ / 2, NA = (BX + 2) * 2;
   constexpr int DCH = 8 * MT, DROWS = NT / DCH, ND = NVB / DROWS;
@@ -435,9 +449,11 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_halo2_kernel(const WgradHalo
   const int a_r = min(tid >> 3, RPP - 1), a_c4 = tid & 7;
   const int d_r = tid / DCH, d_c4 = tid % DCH;
   float4 rs[NCH];
-  int X0 = 0, Y0 = 0, Z0 = 0;                                     // origin of the brick being loaded
+  int X0 = 0, Y0 = 0, Z0 = 0, XS0 = 0;                            // origin of the brick being loaded; first x slab of its scene in x and dy
   unsigned a_voff[2];
-  auto load_begin = [&](int b) {
+  auto load_begin = [&](int bg) {
+    const int sc = bg / p.bricks_per_scene, b = bg - sc * p.bricks_per_scene;
+    XS0 = sc * p.gx;
     const int bk = b % nbz, bj = (b / nbz) % nby, bi = b / (nbz * nby);
     X0 = bi * BX; Y0 = bj * BY; Z0 = bk * BZ;
 #pragma unroll
@@ -453,12 +469,12 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_halo2_kernel(const WgradHalo
       const int slab = c >> 1, j = c & 1;
       const int x = X0 + slab - 1;                                                      // uniform
       const bool xin = x >= 0 && x < p.gx;
-      v = __builtin_amdgcn_raw_buffer_load_b128(xr, xin ? a_voff[j] : OOB, xin ? (int)((unsigned)x * (unsigned)(p.gy * p.gz) * (unsigned)p.Cin * 4u) : 0, 0);
+      v = __builtin_amdgcn_raw_buffer_load_b128(xr, xin ? a_voff[j] : OOB, xin ? (int)((unsigned)(XS0 + x) * (unsigned)(p.gy * p.gz) * (unsigned)p.Cin * 4u) : 0, 0);
     } else {
       const int vx = (c - NA) * DROWS + d_r, r = vx % (BY * BZ);
       const int x = X0 + vx / (BY * BZ), y = Y0 + r / BZ, z = Z0 + r % BZ;
       const bool in = x < p.gx && y < p.gy && z < p.gz;
-      const unsigned voff = in ? ((unsigned)((x * p.gy + y) * p.gz + z) * (unsigned)p.Cout + co0 + d_c4 * 4) * 4u : OOB;
+      const unsigned voff = in ? ((unsigned)(((XS0 + x) * p.gy + y) * p.gz + z) * (unsigned)p.Cout + co0 + d_c4 * 4) * 4u : OOB;
       v = __builtin_amdgcn_raw_buffer_load_b128(dr, voff, 0, 0);
     }
     rs[c] = make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
@@ -622,13 +638,16 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_halo2_kernel(const WgradHalo
 }
 
 // wgrad_halo: 3x3x3 stride-1 layers with Cin, Cout multiples of 32: 1 double-buffered halo form, 2 single-buffered, 0 tile kernel
-static bool wgrad_halo_geometry(WgradHaloParams &h, int &mt, int ix, int iy, int iz, int Cin, int Cout, int ksize, int stride) {
+// (the form is chosen from the per-scene grid; the bricks of all scenes are one range, split over the workgroups of the launch)
+static bool wgrad_halo_geometry(WgradHaloParams &h, int &mt, int ix, int iy, int iz, int Cin, int Cout, int ksize, int stride, int scenes = 1) {
   if (!g_tune_wgrad_halo || ksize != 3 || stride != 1 || (Cin & 31) || (Cout & 31)) return false;
-  if ((int64_t)ix * iy * iz * (Cin > Cout ? Cin : Cout) * 4 >= 0xfffffff0ll - 65536) return false;
+  if ((int64_t)scenes * ix * iy * iz * (Cin > Cout ? Cin : Cout) * 4 >= 0xfffffff0ll - 65536) return false;
   h.Cin = Cin; h.Cout = Cout; h.gx = ix; h.gy = iy; h.gz = iz;
   const bool db = g_tune_wgrad_halo == 1;                                       // double-buffered form (default): bricks of 4 x 8 x 4
-  h.nbricks = ceil_div(ix, db ? 4 : 8) * ceil_div(iy, 8) * ceil_div(iz, 4);
-  if ((int64_t)h.nbricks * (db ? 128 : 256) > (int64_t)2 * ix * iy * iz) return false;       // bricks mostly padding: the tile kernel wins
+  h.scenes = scenes;
+  h.bricks_per_scene = ceil_div(ix, db ? 4 : 8) * ceil_div(iy, 8) * ceil_div(iz, 4);
+  h.nbricks = scenes * h.bricks_per_scene;
+  if ((int64_t)h.bricks_per_scene * (db ? 128 : 256) > (int64_t)2 * ix * iy * iz) return false;       // bricks mostly padding: the tile kernel wins
   mt = (Cout & 63) ? 1 : 2;
   const int tiles = (Cout / (32 * mt)) * (Cin / 32);
   const int splits = std::max(1, std::min(h.nbricks / 4, ceil_div(256, tiles)));      // fill the chip; >= 4 bricks per workgroup
@@ -650,7 +669,10 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float4 *__restr
 // Reduction rows, K steps, split count and the carried-coordinate digits of a geometry whose (ox, oy, oz), taps and channel counts are set.
 static int wgrad_split_plan(WgradParams &p, const char *who) {
   const int Cin = p.Cin, Cout = p.Cout;
-  p.OV = p.ox * p.oy * p.oz;
+  if (p.scenes < 1) p.scenes = 1;
+  const int OV1 = p.ox * p.oy * p.oz;
+  if ((int64_t)p.scenes * OV1 >= ((int64_t)1 << 30)) return set_error(SGC_EUNSUP, "%s: too many rows", who);
+  p.OV = p.scenes * OV1;
   p.ksteps = ceil_div(p.OV, 32);
   const int tiles = ceil_div(Cout, 128) * ceil_div(Cin, 128) * p.taps;
   int splits = 1;
@@ -660,13 +682,16 @@ static int wgrad_split_plan(WgradParams &p, const char *who) {
   while (tiles * splits < 256 && p.ksteps / (splits * 2) >= 3) splits *= 2;
   p.steps_per_split = ceil_div(p.ksteps, splits);
   p.splits = ceil_div(p.ksteps, p.steps_per_split);
-  p.ax = 32 / (p.oy * p.oz); p.by = (32 % (p.oy * p.oz)) / p.oz; p.cz = 32 % p.oz;
-  if ((int64_t)p.OV * Cout * 4 >= 0xfffffff0ll - 65536 || (int64_t)p.ix * p.iy * p.iz * Cin * 4 >= 0xfffffff0ll - 65536)
+  p.by = (32 % (p.oy * p.oz)) / p.oz; p.cz = 32 % p.oz;
+  if (p.scenes > 1) { p.as = 32 / OV1; p.ax = (32 % OV1) / (p.oy * p.oz); }      // a batch carries a scene digit above x
+  else { p.as = 0; p.ax = 32 / (p.oy * p.oz); }
+  if ((int64_t)p.OV * Cout * 4 >= 0xfffffff0ll - 65536 || (int64_t)p.scenes * p.ix * p.iy * p.iz * Cin * 4 >= 0xfffffff0ll - 65536)
     return set_error(SGC_EUNSUP, "%s: x and dy must stay below 4 GiB each", who);
   return SGC_OK;
 }
 
-static int wgrad_geometry(WgradParams &p, int ix, int iy, int iz, int Cin, int Cout, int ksize, int stride) {
+static int wgrad_geometry(WgradParams &p, int ix, int iy, int iz, int Cin, int Cout, int ksize, int stride, int scenes = 1) {
+  p.scenes = scenes;
   if (Cin <= 0 || Cout <= 0 || ix <= 0 || iy <= 0 || iz <= 0) return set_error(SGC_EINVAL, "sgc_conv3d_wgrad_bf16x3: bad size");
   if ((Cin & 3) || (Cout & 3)) return set_error(SGC_EUNSUP, "sgc_conv3d_wgrad_bf16x3: Cin and Cout must be multiples of 4");
   if (ksize == 2) {
@@ -712,11 +737,19 @@ static int wgrad_tile_launch(WgradParams &p, const float *x, const float *dy, fl
   const size_t smem = (size_t)2 * 4 * 128 * LDKH * sizeof(uint16_t);
   static std::atomic<uint64_t> attr_done{0};
   static std::atomic<uint64_t> attr_done8{0};
-  ensure_dynamic_lds((const void *)conv3d_wgrad_bf16x3_kernel<2, IMG>, (int)smem, attr_done);
-  ensure_dynamic_lds((const void *)conv3d_wgrad_bf16x3_kernel<4, IMG>, (int)smem, attr_done8);
   const dim3 wgrid(ceil_div(p.Cout, 128), ceil_div(p.Cin, 128), p.taps * p.splits);
-  if (g_tune_wgrad_waves == 8) hipLaunchKernelGGL((conv3d_wgrad_bf16x3_kernel<4, IMG>), wgrid, dim3(512), smem, st, p);
-  else hipLaunchKernelGGL((conv3d_wgrad_bf16x3_kernel<2, IMG>), wgrid, dim3(256), smem, st, p);
+  if (!IMG && p.scenes > 1) {                              // a batch of volumes: the kernels with the scene digit
+    static std::atomic<uint64_t> attr_sc{0}, attr_sc8{0};
+    ensure_dynamic_lds((const void *)conv3d_wgrad_bf16x3_kernel<2, false, true>, (int)smem, attr_sc);
+    ensure_dynamic_lds((const void *)conv3d_wgrad_bf16x3_kernel<4, false, true>, (int)smem, attr_sc8);
+    if (g_tune_wgrad_waves == 8) hipLaunchKernelGGL((conv3d_wgrad_bf16x3_kernel<4, false, true>), wgrid, dim3(512), smem, st, p);
+    else hipLaunchKernelGGL((conv3d_wgrad_bf16x3_kernel<2, false, true>), wgrid, dim3(256), smem, st, p);
+  } else {
+    ensure_dynamic_lds((const void *)conv3d_wgrad_bf16x3_kernel<2, IMG>, (int)smem, attr_done);
+    ensure_dynamic_lds((const void *)conv3d_wgrad_bf16x3_kernel<4, IMG>, (int)smem, attr_done8);
+    if (g_tune_wgrad_waves == 8) hipLaunchKernelGGL((conv3d_wgrad_bf16x3_kernel<4, IMG>), wgrid, dim3(512), smem, st, p);
+    else hipLaunchKernelGGL((conv3d_wgrad_bf16x3_kernel<2, IMG>), wgrid, dim3(256), smem, st, p);
+  }
   int rc = check_launch("conv3d_wgrad_bf16x3_kernel");
   if (rc) return rc;
   if (p.splits > 1) {
@@ -729,28 +762,36 @@ static int wgrad_tile_launch(WgradParams &p, const float *x, const float *dy, fl
   return rc;
 }
 
-extern "C" int64_t sgc_conv3d_wgrad_workspace_floats(int ix, int iy, int iz, int Cin, int Cout, int ksize, int stride) {
+extern "C" int64_t sgc_conv3d_wgrad_batched_workspace_floats(int ix, int iy, int iz, int Cin, int Cout, int ksize, int stride, int scenes) {
+  if (scenes < 1) return -1;
   WgradHaloParams h = {};
   int mt = 1;
-  if (wgrad_halo_geometry(h, mt, ix, iy, iz, Cin, Cout, ksize, stride)) {
+  if (wgrad_halo_geometry(h, mt, ix, iy, iz, Cin, Cout, ksize, stride, scenes)) {
     const int splits = ceil_div(h.nbricks, h.bricks_per_split);
     return splits > 1 ? (int64_t)splits * 27 * Cout * Cin : 0;
   }
   WgradParams p = {};
-  if (wgrad_geometry(p, ix, iy, iz, Cin, Cout, ksize, stride)) return -1;
+  if (wgrad_geometry(p, ix, iy, iz, Cin, Cout, ksize, stride, scenes)) return -1;
   return p.splits > 1 ? (int64_t)p.splits * p.taps * Cout * Cin : 0;
 }
+extern "C" int64_t sgc_conv3d_wgrad_workspace_floats(int ix, int iy, int iz, int Cin, int Cout, int ksize, int stride) {
+  return sgc_conv3d_wgrad_batched_workspace_floats(ix, iy, iz, Cin, Cout, ksize, stride, 1);
+}
 
-extern "C" int sgc_conv3d_wgrad_bf16x3(const float *x, const float *dy, float *dw, int ix, int iy, int iz, int Cin, int Cout,
-                                       int ksize, int stride, float *workspace_or_null, int64_t workspace_floats,
-                                       sgc_stream_t stream) {
+// The weight gradient of a scene batch: x [scenes * ix*iy*iz, Cin] and dy [scenes * OV, Cout] (scene s first), dw summed over the
+// scenes INSIDE the launch -- to the kernels the scene axis is more reduction rows (tile kernel) or more bricks (halo forms); no
+// tap crosses a scene's border.  scenes = 1 IS sgc_conv3d_wgrad_bf16x3.
+extern "C" int sgc_conv3d_wgrad_bf16x3_batched(const float *x, const float *dy, float *dw, int ix, int iy, int iz, int Cin, int Cout,
+                                               int ksize, int stride, int scenes, float *workspace_or_null, int64_t workspace_floats,
+                                               sgc_stream_t stream) {
   if (!x || !dy || !dw) return set_error(SGC_EINVAL, "sgc_conv3d_wgrad_bf16x3: null pointer");
+  if (scenes < 1) return set_error(SGC_EINVAL, "sgc_conv3d_wgrad_bf16x3_batched: scenes must be >= 1");
   if (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dw | (uintptr_t)workspace_or_null) & 15)
     return set_error(SGC_EINVAL, "sgc_conv3d_wgrad_bf16x3: pointers must be 16-byte aligned");
   hipStream_t st0 = (hipStream_t)stream;
   WgradHaloParams h = {};
   int mt = 1;
-  if (wgrad_halo_geometry(h, mt, ix, iy, iz, Cin, Cout, ksize, stride)) {
+  if (wgrad_halo_geometry(h, mt, ix, iy, iz, Cin, Cout, ksize, stride, scenes)) {
     int splits = ceil_div(h.nbricks, h.bricks_per_split);
     const int64_t n27 = (int64_t)27 * Cout * Cin;
     if (splits > 1 && !(workspace_or_null && workspace_floats >= splits * n27)) { splits = 1; h.bricks_per_split = h.nbricks; }
@@ -786,9 +827,15 @@ extern "C" int sgc_conv3d_wgrad_bf16x3(const float *x, const float *dy, float *d
     return rch;
   }
   WgradParams p = {};
-  int rc = wgrad_geometry(p, ix, iy, iz, Cin, Cout, ksize, stride);
+  int rc = wgrad_geometry(p, ix, iy, iz, Cin, Cout, ksize, stride, scenes);
   if (rc) return rc;
   return wgrad_tile_launch<false>(p, x, dy, dw, workspace_or_null, workspace_floats, stream);
+}
+
+extern "C" int sgc_conv3d_wgrad_bf16x3(const float *x, const float *dy, float *dw, int ix, int iy, int iz, int Cin, int Cout,
+                                       int ksize, int stride, float *workspace_or_null, int64_t workspace_floats,
+                                       sgc_stream_t stream) {
+  return sgc_conv3d_wgrad_bf16x3_batched(x, dy, dw, ix, iy, iz, Cin, Cout, ksize, stride, 1, workspace_or_null, workspace_floats, stream);
 }
 
 extern "C" int64_t sgc_conv2d_wgrad_workspace_floats(int N, int H, int W, int Cin, int Cout, int ksize, int stride) {

@@ -33,7 +33,10 @@ struct ConvParams {
   int taps;               // ksize^3
   int splitk;             // number of tap groups (divides taps); >1 -> atomic accumulate, no epilogue
   int steps_per;          // bf16x3 tile kernel, splitk > 1: K steps (32 channels of one tap) per split; the last split may hold fewer
-  int M;                  // gx*gy*gz
+  int M;                  // gx*gy*gz: GEMM rows of ONE scene
+  int scenes;             // volumes of one launch (sgc_conv3d_cl_bf16x3_batched): x holds scenes * ix*iy*iz rows, y / residual / a workspace
+                          // slab scenes * OV rows, scene s first; a workgroup's halo ends at its scene's border.  The tile kernel walks
+                          // M * scenes GEMM rows and decodes the scene per row; the halo kernels launch scenes * bricks workgroups
   float *ws;              // optional split-K workspace [splitk][OV][Cout]: every split stores its partial tile there and
   int64_t ws_stride;      // the epilogue kernel sums them in split order (deterministic); null: float atomics into y
   int64_t ws_floats;      // capacity of ws

@@ -377,19 +377,23 @@ class ChannelsLastConv3dFunction(Function):
       zero-interleaved dy (dy at the even fine-grid positions: 8x the necessary matrix work on two small layers, no new
       kernel -- the two stride-2 layers are 6 % of the neck's FLOPs);
     * weight gradient: ``sgc_conv3d_wgrad_bf16x3``.
+
+    ``scenes`` > 1 (training on scene batches): x holds that many volumes of ``grid`` one after the other
+    ([scenes * X*Y*Z, Cin]) and so do y and both gradients; every pass is ONE launch of the ``_batched`` entries and the weight
+    gradient -- one per layer, not one per scene -- is summed over the scenes inside its kernel.
     """
 
     @staticmethod
-    def forward(ctx, x, weight, grid, ksize, stride):
+    def forward(ctx, x, weight, grid, ksize, stride, scenes=1):
         _require_bf16_planes("ChannelsLastConv3dFunction")
         ops = ext.ops()
         cout, cin = weight.shape[:2]
         # parameter [Cout, Cin, k, k, k] -> the kernel's [taps, Cout (multiple of 4), Cin] bf16 hi / lo planes in ONE launch
         hi, lo = _TRAIN_PLANES.get(weight, pad_rows=4)
         x = x.float().contiguous()
-        y, og = ops.conv3d_cl_bf16x3(x, hi, lo, grid, ksize, stride)
+        y, og = ops.conv3d_cl_bf16x3(x, hi, lo, grid, ksize, stride, scenes=scenes)
         ctx.save_for_backward(x, weight)
-        ctx.geom = (tuple(grid), tuple(og), ksize, stride)
+        ctx.geom = (tuple(grid), tuple(og), ksize, stride, int(scenes))
         return y[:, :cout] if y.shape[1] != cout else y
 
     @staticmethod
@@ -397,7 +401,7 @@ class ChannelsLastConv3dFunction(Function):
     def backward(ctx, dy):
         ops = ext.ops()
         x, weight = ctx.saved_tensors
-        grid, og, ksize, stride = ctx.geom
+        grid, og, ksize, stride, scenes = ctx.geom
         cout, cin = weight.shape[:2]
         dy = dy.float().contiguous()
         dx = dw = None
@@ -407,17 +411,17 @@ class ChannelsLastConv3dFunction(Function):
             hi, lo = _TRAIN_PLANES.get(weight, transpose=True, flip=True, pad_cols=32)
             g = _pad_cols(dy, 32)
             if stride == 2:
-                up = torch.zeros((grid[0], grid[1], grid[2], g.shape[1]), dtype=torch.float32, device=dy.device)
-                up[:2 * og[0]:2, :2 * og[1]:2, :2 * og[2]:2] = g.view(og[0], og[1], og[2], -1)
+                up = torch.zeros((scenes, grid[0], grid[1], grid[2], g.shape[1]), dtype=torch.float32, device=dy.device)
+                up[:, :2 * og[0]:2, :2 * og[1]:2, :2 * og[2]:2] = g.view(scenes, og[0], og[1], og[2], -1)
                 g = up.view(-1, g.shape[1])
-            dx, _ = ops.conv3d_cl_bf16x3(g.contiguous(), hi, lo, grid, ksize, 1)
+            dx, _ = ops.conv3d_cl_bf16x3(g.contiguous(), hi, lo, grid, ksize, 1, scenes=scenes)
         if ctx.needs_input_grad[1]:
             # the halo form of the weight gradient wants 32-channel dy tiles: the head's 3 x 3 x 3 convolutions (Cout = 28 ...)
             # get four zero columns rather than the per-tap tile kernel
             mult = 32 if ksize == 3 and stride == 1 and cin % 32 == 0 else 4
-            dwk = ops.conv3d_wgrad_bf16x3(x, _pad_cols(dy, mult).contiguous(), grid, ksize, stride)     # [taps, cout_p, cin]
+            dwk = ops.conv3d_wgrad_bf16x3(x, _pad_cols(dy, mult).contiguous(), grid, ksize, stride, scenes=scenes)     # [taps, cout_p, cin]
             dw = ops.unpack_conv_wgrad(dwk, weight.shape).to(weight.dtype)
-        return dx, dw, None, None, None
+        return dx, dw, None, None, None, None
 
 
 def _conv2d_rows(*args, **kwargs):
@@ -597,18 +601,18 @@ class ChannelsLastConvTranspose3dFunction(Function):
     """``nn.ConvTranspose3d(2, 2, bias=False)`` on channels-last rows (up_block_*, necks/imvoxelnet.py:56-58): forward on the
     parity form of the MFMA kernel, input gradient = the k2 s2 convolution of dy, weight gradient =
     ``sgc_conv3d_wgrad_bf16x3`` with the roles of the two tensors exchanged.  x [X*Y*Z, Cin], weight [Cin, Cout, 2, 2, 2]
-    -> y [8*X*Y*Z, Cout]; Cin % 32 == 0, Cout % 32 == 0."""
+    -> y [8*X*Y*Z, Cout]; Cin % 32 == 0, Cout % 32 == 0.  ``scenes`` as in ``ChannelsLastConv3dFunction``."""
 
     @staticmethod
-    def forward(ctx, x, weight, grid):
+    def forward(ctx, x, weight, grid, scenes=1):
         _require_bf16_planes("ChannelsLastConvTranspose3dFunction")
         ops = ext.ops()
         cin, cout = weight.shape[:2]
         hi, lo = _TRAIN_PLANES.get(weight, transpose=True)            # [Cin, Cout, 8] -> [8, Cout, Cin]
         x = x.float().contiguous()
-        y, og = ops.conv3d_cl_bf16x3(x, hi, lo, grid, 2, 2, True)
+        y, og = ops.conv3d_cl_bf16x3(x, hi, lo, grid, 2, 2, True, scenes=scenes)
         ctx.save_for_backward(x, weight)
-        ctx.geom = (tuple(grid), tuple(og))
+        ctx.geom = (tuple(grid), tuple(og), int(scenes))
         return y
 
     @staticmethod
@@ -616,17 +620,17 @@ class ChannelsLastConvTranspose3dFunction(Function):
     def backward(ctx, dy):
         ops = ext.ops()
         x, weight = ctx.saved_tensors
-        grid, og = ctx.geom
+        grid, og, scenes = ctx.geom
         cin, cout = weight.shape[:2]
         dy = dy.float().contiguous()
         dx = dw = None
         if ctx.needs_input_grad[0]:
             hi, lo = _TRAIN_PLANES.get(weight)                        # [Cin, Cout, 8] -> [8, Cin, Cout]
-            dx, _ = ops.conv3d_cl_bf16x3(dy, hi, lo, og, 2, 2)                  # dx[x] = sum_p dy[2x + p] W[:, :, p]^T
+            dx, _ = ops.conv3d_cl_bf16x3(dy, hi, lo, og, 2, 2, scenes=scenes)   # dx[x] = sum_p dy[2x + p] W[:, :, p]^T
         if ctx.needs_input_grad[1]:
-            dwk = ops.conv3d_wgrad_bf16x3(dy, x, og, 2, 2)                      # [8, cin, cout]
+            dwk = ops.conv3d_wgrad_bf16x3(dy, x, og, 2, 2, scenes=scenes)       # [8, cin, cout]
             dw = ops.unpack_conv_wgrad(dwk, weight.shape).to(weight.dtype)
-        return dx, dw, None
+        return dx, dw, None, None
 
 
 class BatchNormRowsFunction(Function):

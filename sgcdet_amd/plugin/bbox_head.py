@@ -113,13 +113,14 @@ class ImVoxelHeadV2(nn.Module):
         """Training / autograd path on the HIP kernels: the three 3x3x3 convolutions of a scale as ONE convolution with the
         concatenated weights (autograd splits the weight gradient back), imvoxel_head_v2.py:75-78,103-110."""
         # not one walker with _forward_hip: there a folded bias and exp in the kernel's epilogue, here torch ops and an ephemeral plane
-        from ..functions import ChannelsLastConv3dFunction, train_weight_planes
+        from ..functions import train_weight_planes
+        from .conv_plan import train_conv3d_rows
         w, n_reg = self._fused_weight()
         train_weight_planes().mark_ephemeral(w)          # a fresh temporary every step: packed per use (once for the three scales), never registered
         ctr, reg, cls = [], [], []
         for x, scale in zip(feats, self.scales):
             rows, grid = to_channels_last_rows(x)
-            y = ChannelsLastConv3dFunction.apply(rows, w, tuple(grid), 3, 1)
+            y = train_conv3d_rows(rows, w, tuple(grid), 3, 1, scenes=x.shape[0])       # the scenes of a batch in one launch per pass
             full = rows_to_ncdhw(y, grid, y.shape[1])
             ctr.append(full[:, :1])
             reg.append(self._reg_activation(full[:, 1:1 + n_reg], scale))
@@ -127,8 +128,13 @@ class ImVoxelHeadV2(nn.Module):
         return ctr, reg, cls
 
     def forward(self, x, valid_masks=None):
-        if not self.training and not torch.is_grad_enabled() and x[0].is_cuda and x[0].shape[0] == 1:
-            return self._forward_hip(x, valid_masks)
+        if not self.training and not torch.is_grad_enabled() and x[0].is_cuda:
+            if x[0].shape[0] == 1:
+                return self._forward_hip(x, valid_masks)
+            # a batch in eval: the single-scene lowering scene by scene (masks and the fused activation as they are), bit-identical
+            # to B separate calls; ``valid_masks``: one list of per-scale masks per scene
+            per = [self._forward_hip([f[b:b + 1] for f in x], None if valid_masks is None else valid_masks[b]) for b in range(x[0].shape[0])]
+            return tuple([torch.cat([p[k][i] for p in per]) for i in range(len(x))] for k in range(3))
         if train_conv_on_hip(x[0], [self.cls_conv.in_channels]):
             return self._forward_autograd_hip(x)
         return multi_apply(self.forward_single, [t.contiguous() for t in x], self.scales)   # packed NCDHW for MIOpen

@@ -279,6 +279,12 @@ class BiasConv2d:
 TRAIN_CONV = os.environ.get("SGC_TRAIN_CONV", "hip")
 BN_ON_HIP = os.environ.get("SGC_BN_HIP", "1") != "0"      # training-mode BatchNorm of the neck on sgc_bn_rows_* (0: torch's kernels)
 BN_FUSE_TAIL = os.environ.get("SGC_BN_FUSE_TAIL", "1") != "0"   # `+ identity` / ReLU behind a BatchNorm inside its passes (0: torch ops, A/B)
+# a batch of scenes through a training convolution: "batched" = one launch per pass on the `_batched` entries, the
+# weight gradient summed over the scenes inside its kernel; "loop" = the scene-less entries scene by scene (B launches per pass, B
+# weight gradients added by autograd) around the same joint norm -- the timing baseline and a second checker
+TRAIN_SCENE_BATCH = os.environ.get("SGC_TRAIN_SCENE_BATCH", "batched")
+if TRAIN_SCENE_BATCH not in ("batched", "loop"):
+    raise ValueError(f"SGC_TRAIN_SCENE_BATCH={TRAIN_SCENE_BATCH}: batched or loop")
 
 
 THROUGHPUT_GEOMETRY = False      # set_throughput_mode(True): scenes in flight, kernels sized for CU-time
@@ -319,10 +325,31 @@ def set_train_conv(mode):
     TRAIN_CONV = mode
 
 
+def set_train_scene_batch(mode):
+    global TRAIN_SCENE_BATCH
+    if mode not in ("batched", "loop"):
+        raise ValueError(mode)
+    TRAIN_SCENE_BATCH = mode
+
+
 def train_conv_on_hip(x, channels):
-    """Can the autograd path of a conv chain run on the HIP kernels?  (one scene, CUDA, channel counts the K tile accepts)"""
-    return (TRAIN_CONV == "hip" and CONV_MODE == "bf16x3" and train_products_ok() and x.is_cuda and x.shape[0] == 1
+    """Can the autograd path of a conv chain run on the HIP kernels?  (CUDA, any number of scenes, channel counts the K tile accepts)"""
+    return (TRAIN_CONV == "hip" and CONV_MODE == "bf16x3" and train_products_ok() and x.is_cuda and x.shape[0] >= 1
             and all(c % _PAD == 0 for c in channels))
+
+
+def train_conv3d_rows(x, weight, grid, ksize=3, stride=1, transposed=False, scenes=1):
+    """A training convolution on the rows of ``scenes`` volumes of ``grid`` ([scenes * V, Cin] -> [scenes * OV, Cout]) under autograd,
+    by ``TRAIN_SCENE_BATCH``: one Function call on the batch, or one per scene."""
+    from ..functions import ChannelsLastConv3dFunction, ChannelsLastConvTranspose3dFunction
+    batched = scenes == 1 or TRAIN_SCENE_BATCH == "batched"
+    parts = (x,) if batched else x.view(scenes, -1, x.shape[1]).unbind(0)
+    n = scenes if batched else 1
+    if transposed:
+        out = [ChannelsLastConvTranspose3dFunction.apply(rows, weight, grid, n) for rows in parts]
+    else:
+        out = [ChannelsLastConv3dFunction.apply(rows, weight, grid, ksize, stride, n) for rows in parts]
+    return out[0] if batched else torch.cat(out)
 
 
 def train_products_ok():
@@ -396,8 +423,8 @@ def bn_rows(bn, rows, grid, residual=None, relu=False, image=False, channels=Non
     if image:
         y = bn(rows.view(grid[0], grid[1], grid[2], rows.shape[1]).permute(0, 3, 1, 2))
         return tail(y.permute(0, 2, 3, 1).reshape(rows.shape[0], rows.shape[1]))
-    y = bn(rows_to_ncdhw(rows, grid, rows.shape[1]))
-    return tail(y[0].permute(1, 2, 3, 0).reshape(rows.shape[0], rows.shape[1]))
+    y = bn(rows_to_ncdhw(rows, grid, rows.shape[1]))           # [B, C, X, Y, Z]: a SyncBatchNorm3d sees the batch it was written for
+    return tail(y.permute(0, 2, 3, 4, 1).reshape(rows.shape[0], rows.shape[1]))
 
 
 def _bn_rows_padded(bn, rows, grid, residual, relu, image, C, relu_then_add):
@@ -520,22 +547,23 @@ class TrainStem7:
 class TrainConv3d:
     """To training what ``ConvSpec`` is to eval, with its call signature: an ``nn.Conv3d`` (k in {1, 3}, padding k // 2) or
     ``nn.ConvTranspose3d(2, 2, bias=False)`` with a LIVE norm behind it, under autograd on channels-last rows.  Holds the two modules
-    and nothing else: the weight is read through ``train_weight_planes()`` at every call, the norm is whatever ``bn_rows`` takes."""
+    and nothing else: the weight is read through ``train_weight_planes()`` at every call, the norm is whatever ``bn_rows`` takes.
+    ``scenes``: the rows hold that many volumes of the grid, one after the other; the convolution treats each on its own
+    (``train_conv3d_rows``), the norm sees the rows of all of them -- the statistics of the batch."""
 
-    def __init__(self, conv, bn):
-        self.conv, self.bn, self.cout = conv, bn, conv.out_channels
+    def __init__(self, conv, bn, scenes=1):
+        self.conv, self.bn, self.cout, self.scenes = conv, bn, conv.out_channels, int(scenes)
 
     def __call__(self, x, grid, residual=None, relu=0, out_mask=None, act=None):
         """``relu`` as ``ConvSpec`` has it -- 0: bn + residual; 1: relu(bn + residual); 2: relu(bn), then + residual."""
-        from ..functions import ChannelsLastConv3dFunction, ChannelsLastConvTranspose3dFunction
         if out_mask is not None or act is not None:
             raise NotImplementedError("TrainConv3d: row masks and the output activation are eval-only (ConvSpec)")
         conv, grid = self.conv, tuple(grid)
         if isinstance(conv, torch.nn.ConvTranspose3d):
-            y, og = ChannelsLastConvTranspose3dFunction.apply(x, conv.weight, grid), tuple(2 * d for d in grid)
+            y, og = train_conv3d_rows(x, conv.weight, grid, transposed=True, scenes=self.scenes), tuple(2 * d for d in grid)
         else:
             k, s = conv.kernel_size[0], conv.stride[0]
-            y, og = ChannelsLastConv3dFunction.apply(x, conv.weight, grid, k, s), tuple((d + 2 * (k // 2) - k) // s + 1 for d in grid)
+            y, og = train_conv3d_rows(x, conv.weight, grid, k, s, scenes=self.scenes), tuple((d + 2 * (k // 2) - k) // s + 1 for d in grid)
             if conv.bias is not None:
                 y = y + conv.bias
         if relu == 2:
@@ -575,10 +603,10 @@ def image_rows(x):
 
 
 def to_channels_last_rows(x):
-    """[1,C,X,Y,Z] (any strides) -> ([X*Y*Z, C_padded] contiguous rows, (X,Y,Z)); no copy when the
-    tensor already is channels-last in memory and C % 32 == 0."""
-    _, C, X, Y, Z = x.shape
-    rows = x[0].permute(1, 2, 3, 0).reshape(X * Y * Z, C)          # view if channels-last, copy otherwise
+    """[B,C,X,Y,Z] (any strides) -> ([B*X*Y*Z, C_padded] contiguous rows, scene b in rows [b*X*Y*Z, (b+1)*X*Y*Z); (X,Y,Z)); no copy
+    when the tensor already is channels-last in memory and C % 32 == 0."""
+    B, C, X, Y, Z = x.shape
+    rows = x.permute(0, 2, 3, 4, 1).reshape(B * X * Y * Z, C)      # view if channels-last, copy otherwise
     cp = _pad_to(C)
     if cp != C:
         rows = torch.nn.functional.pad(rows, (0, cp - C))
@@ -586,9 +614,9 @@ def to_channels_last_rows(x):
 
 
 def rows_to_ncdhw(rows, grid, channels):
-    """[V, Cp] rows -> [1, channels, X, Y, Z] view (channels-last memory, no copy)."""
+    """[B*V, Cp] rows -> [B, channels, X, Y, Z] view (channels-last memory, no copy); B = rows / V."""
     X, Y, Z = grid
-    return rows.view(X, Y, Z, rows.shape[1])[..., :channels].permute(3, 0, 1, 2).unsqueeze(0)
+    return rows.view(-1, X, Y, Z, rows.shape[1])[..., :channels].permute(0, 4, 1, 2, 3)
 
 
 class BlockDiagSpec:

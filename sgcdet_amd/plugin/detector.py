@@ -66,11 +66,11 @@ class SGCDet(nn.Module):
             raise NotImplementedError("SGCDet: head_2d is not built (the SGCDet configs set none)")
 
     def extract_img_feat(self, img):
-        """img [B, N, 3, H, W] -> FPN maps [[B, N, C, H_l, W_l], ...] (SGCDet.py:62-69, B = 1 as there)."""
+        """img [B, N, 3, H, W] -> FPN maps [[B, N, C, H_l, W_l], ...] (SGCDet.py:62-69).  The reference's voxel head is batch 1 by
+        assertion and its step is one scene per rank; here a batch is B scenes on one device: the image side sees
+        B * N images, the voxel head runs scene by scene, neck_3d and the head on the batch."""
         self._need_backbone("extract_img_feat")
-        if img.shape[0] != 1:
-            raise NotImplementedError("SGCDet: batch size 1, as the reference's voxel head")
-        return self.image_features(self.backbone(img.reshape([-1] + list(img.shape)[2:])))
+        return self.image_features(self.backbone(img.reshape([-1] + list(img.shape)[2:])), batch=img.shape[0])
 
     def build_volume(self, batch):
         """SGCDet.build_volume (SGCDet.py:61-94): ``batch`` = dict(img [B,N,3,H,W], img_metas, depth_maps for ``use_gt_dpt``)
@@ -106,13 +106,15 @@ class SGCDet(nn.Module):
         finally:
             self._step_begun = False
 
-    def image_features(self, backbone_feats):
-        """Backbone maps [[B*N, C_l, H_l, W_l], ...] -> [[B, N, C, H, W], ...] as SGCDet.py:67-69 with B = 1.  In eval mode on
+    def image_features(self, backbone_feats, batch=1):
+        """Backbone maps [[B*N, C_l, H_l, W_l], ...] -> [[B, N, C, H, W], ...] as SGCDet.py:67-69.  In eval mode on
         the GPU the FPN's convolutions emit channels-last memory (plugin/fpn.py), which the view transformation reads in
-        place; the reshape keeps that memory format."""
+        place; the reshape keeps that memory format (per scene: ``f[b:b+1]`` of a batch is the B = 1 tensor of scene b)."""
         if self.neck is None:
             raise RuntimeError("SGCDet.image_features: the config has no FPN neck")
-        return [f.unsqueeze(0) for f in self.neck(backbone_feats)]
+        if batch == 1:
+            return [f.unsqueeze(0) for f in self.neck(backbone_feats)]
+        return [f.unflatten(0, (batch, -1)) for f in self.neck(backbone_feats)]
 
     @staticmethod
     def depth_pyramid(dpt_dist):
@@ -155,7 +157,17 @@ class SGCDet(nn.Module):
             # a training step begins: every weight plane the HIP training Functions have registered is repacked in ONE launch
             from ..functions import train_weight_planes
             train_weight_planes().begin_step()
-        volume, valid, occ = self.voxel_head(x, img_metas[0], self.depth_pyramid(dpt_dist))
+        B = x[0].shape[0]
+        if B == 1:
+            volume, valid, occ = self.voxel_head(x, img_metas[0], self.depth_pyramid(dpt_dist))
+        else:
+            if len(img_metas) != B or dpt_dist.shape[0] != B:
+                raise RuntimeError(f"SGCDet: {B} scenes of feature maps, {len(img_metas)} img_metas, {dpt_dist.shape[0]} depth distributions")
+            # the voxel head is batch 1 (AdaptiveSparseHead.py:45, DenseHead.py:60): scene by scene, stacked
+            per = [self.voxel_head([f[b:b + 1] for f in x], img_metas[b], self.depth_pyramid(dpt_dist[b:b + 1])) for b in range(B)]
+            volume = torch.cat([p[0] for p in per])
+            valid = None if any(p[1] is None for p in per) else torch.cat([p[1] for p in per])
+            occ = None if any(p[2] is None for p in per) else torch.cat([p[2] for p in per])
         if valid is None:
             _, _, vh, vw, vz = volume.shape
             valid = torch.ones([volume.shape[0], 1, vh, vw, vz], device=volume.device)
@@ -308,7 +320,18 @@ class SGCDet(nn.Module):
         return entry["result"]
 
     def forward_features(self, x, img_metas, dpt_dist):
-        """FPN maps + depth distribution -> head tensors (the timed hot path)."""
+        """FPN maps + depth distribution -> head tensors (the timed hot path).  A batch in eval / no-grad is this call scene by scene,
+        stacked: bit-identical to B separate calls (graphs, masks and the Winograd form stay as they are)."""
+        if x[0].shape[0] > 1 and not self.training and not torch.is_grad_enabled():
+            per = []
+            for b in range(x[0].shape[0]):
+                r = self.forward_features([f[b:b + 1] for f in x], img_metas[b:b + 1], dpt_dist[b:b + 1])
+                # graph replays hand out their static buffers: the next scene overwrites them
+                per.append({k: ([t.clone() for t in v] if isinstance(v, (list, tuple)) else None if v is None else v.clone()) for k, v in r.items()})
+            out = {k: None if per[0][k] is None else torch.cat([p[k] for p in per]) for k in ("volume", "valid", "occ")}
+            for k in ("centerness", "bbox_pred", "cls_score"):
+                out[k] = [torch.cat([p[k][i] for p in per]) for i in range(len(per[0][k]))]
+            return out
         if (self.scene_graph and not self.training and not torch.is_grad_enabled() and dpt_dist.is_cuda
                 and self.voxel_head is not None):
             return self._forward_scene_graph(x, img_metas, dpt_dist)

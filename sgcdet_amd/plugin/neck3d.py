@@ -13,6 +13,8 @@ On the GPU the network is described once (``_build_plan(make)``) and walked once
 ``ConvSpec`` layers (cached), training ``TrainConv3d`` layers over the live modules; the torch modules at the end of ``forward`` are
 the reference formulation and the path for everything else.
 """
+import functools
+
 import torch
 from torch import nn
 
@@ -111,13 +113,20 @@ class FastIndoorImVoxelNeck(nn.Module):
         return outs[::-1]
 
     def forward(self, x, tail_masks=None):
-        """[1,C,nx,ny,nz] -> [out@1x, out@1/2, out@1/4], finest first (imvoxelnet.py:22-34)."""
-        if not self.training and not torch.is_grad_enabled() and x.is_cuda and x.shape[0] == 1:
-            return self._run(x, cached_plan(self, lambda: self._build_plan(conv_spec)), tail_masks)
+        """[B,C,nx,ny,nz] -> [out@1x, out@1/2, out@1/4], finest first (imvoxelnet.py:22-34).  In training the norms see the statistics of
+        the batch (the reference's 2-GPU SyncBN step on one device); ``tail_masks`` for B > 1: one pair per scene."""
+        if not self.training and not torch.is_grad_enabled() and x.is_cuda:
+            plan = cached_plan(self, lambda: self._build_plan(conv_spec))
+            if x.shape[0] == 1:
+                return self._run(x, plan, tail_masks)
+            # eval norms couple nothing: the single-scene lowering scene by scene (Winograd, masks and graphs as they are), bit-identical
+            # to B separate calls
+            per = [self._run(x[b:b + 1], plan, None if tail_masks is None else tail_masks[b]) for b in range(x.shape[0])]
+            return [torch.cat(level) for level in zip(*per)]
         if train_conv_on_hip(x, [m.in_channels for m in self.modules() if isinstance(m, (nn.Conv3d, nn.ConvTranspose3d))]):
             # built per forward, never cached: the layers only point at the modules, and a cached list would outlive a
             # convert_sync_batchnorm that replaces the norms
-            return self._run(x, self._build_plan(TrainConv3d))
+            return self._run(x, self._build_plan(functools.partial(TrainConv3d, scenes=x.shape[0])))
         # library convolutions: the voxel head hands over a channels-last strided view, for which MIOpen has only its
         # naive_conv_*_nonpacked kernels (2.6 s per config-2 step instead of ~0.1 s)
         x = x.contiguous()

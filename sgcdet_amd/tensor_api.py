@@ -610,10 +610,13 @@ class TensorOps:
         return self.split_f16(w) if self.lib._dll.sgc_get_conv_products() == 2 else self.split_bf16(w)
 
     def conv3d_cl_bf16x3(self, x, w_hi, w_lo, grid, ksize, stride=1, transposed=False, scale=None, shift=None,
-                         residual=None, relu=False, out=None, out_mask=None, act=None):
+                         residual=None, relu=False, out=None, out_mask=None, act=None, scenes=1):
         """As ``conv3d_cl`` with pre-split bf16 weights (see ``split_bf16``).  ``out_mask`` (uint8 [OV], 3x3x3 stride-1
         layers only): rows with 0 are not needed by the caller (``sgc_conv3d_cl_bf16x3_masked``).  ``act`` = (c0, c1, scale
-        tensor on the device): columns [c0, c1) leave as exp(v * scale) (``sgc_conv3d_cl_bf16x3_act``, 3x3x3 stride 1)."""
+        tensor on the device): columns [c0, c1) leave as exp(v * scale) (``sgc_conv3d_cl_bf16x3_act``, 3x3x3 stride 1).
+        ``scenes`` > 1: x holds that many volumes of ``grid`` one after the other ([scenes * IV, Cin]), y and ``residual``
+        [scenes * OV, Cout]; one launch, every scene convolved on its own (``sgc_conv3d_cl_bf16x3_batched``).  The masked and
+        the activation form have no scene axis."""
         self._check(x=x, w_hi=w_hi, w_lo=w_lo, scale=scale, shift=shift, residual=residual, out_mask=out_mask)
         self._f32(x=x, scale=scale, shift=shift, residual=residual)
         if w_hi.dtype != torch.bfloat16 or w_lo.dtype != torch.bfloat16 or w_hi.shape != w_lo.shape:
@@ -621,18 +624,24 @@ class TensorOps:
         ix, iy, iz = grid
         V, Cin = x.shape
         taps, Cout, Cin2 = w_hi.shape
-        if V != ix * iy * iz or Cin2 != Cin or taps != (8 if transposed else ksize ** 3):
+        scenes = int(scenes)
+        if scenes < 1:
+            raise RuntimeError("conv3d_cl_bf16x3: scenes must be >= 1")
+        if scenes > 1 and (out_mask is not None or act is not None):
+            raise RuntimeError("conv3d_cl_bf16x3: the masked and the activation form take one scene per launch")
+        if V != scenes * ix * iy * iz or Cin2 != Cin or taps != (8 if transposed else ksize ** 3):
             raise RuntimeError("conv3d_cl_bf16x3: inconsistent shapes")
         pad = 0 if ksize == 2 else ksize // 2              # ksize 2 (stride 2): the adjoint geometry of ConvTranspose3d(2, 2)
         og = (2 * ix, 2 * iy, 2 * iz) if transposed else tuple((d + 2 * pad - ksize) // stride + 1 for d in grid)
+        rows = scenes * og[0] * og[1] * og[2]
         if out is not None:
             self._check(out=out)
-            if out.shape != (og[0] * og[1] * og[2], Cout) or out.dtype != torch.float32:
+            if out.shape != (rows, Cout) or out.dtype != torch.float32:
                 raise RuntimeError("conv3d_cl_bf16x3: bad `out` tensor")
-        y = out if out is not None else torch.empty((og[0] * og[1] * og[2], Cout), dtype=torch.float32, device=x.device)
+        y = out if out is not None else torch.empty((rows, Cout), dtype=torch.float32, device=x.device)
         if residual is not None and residual.shape != y.shape:
             raise RuntimeError("conv3d_cl_bf16x3: residual shape mismatch")
-        ws, ws_n = self._conv_workspace(x.device, ix, iy, iz, Cin, Cout, ksize, stride, transposed, 1)
+        ws, ws_n = self._conv_workspace(x.device, ix, iy, iz, Cin, Cout, ksize, stride, transposed, 1, scenes)
         if act is not None:
             c0, c1, act_scale = act
             self._check(act_scale=act_scale)
@@ -650,6 +659,11 @@ class TensorOps:
                 raise RuntimeError("conv3d_cl_bf16x3: out_mask needs a 3x3x3 stride-1 layer and a uint8 mask of [OV]")
             self._call("sgc_conv3d_cl_bf16x3_masked", x, w_hi, w_lo, scale, shift, residual, y, out_mask, ix, iy, iz, Cin,
                        Cout, int(relu), ws, ws_n, _meta=dict(V=V, Cin=Cin, Cout=Cout, taps=taps, OV=y.shape[0], masked=True))
+            return y, og
+        if scenes > 1:
+            self._call("sgc_conv3d_cl_bf16x3_batched", x, w_hi, w_lo, scale, shift, residual, y, ix, iy, iz, Cin, Cout, ksize,
+                       stride, 1 if transposed else 0, int(relu), scenes, ws, ws_n,
+                       _meta=dict(V=V, Cin=Cin, Cout=Cout, taps=taps, OV=y.shape[0], flop_taps=1 if transposed else taps))
             return y, og
         self._call("sgc_conv3d_cl_bf16x3", x, w_hi, w_lo, scale, shift, residual, y, ix, iy, iz, Cin, Cout, ksize,
                    stride, 1 if transposed else 0, int(relu), ws, ws_n,
@@ -1134,9 +1148,11 @@ class TensorOps:
         self._call("sgc_unpack_conv_wgrad", dw_trc.contiguous(), out, A, B, T, R, Cc, int(bool(transpose)), int(bool(flip)))
         return out
 
-    def conv3d_wgrad_bf16x3(self, x, dy, grid, ksize, stride=1):
+    def conv3d_wgrad_bf16x3(self, x, dy, grid, ksize, stride=1, scenes=1):
         """dW [ksize^3, Cout, Cin] of the channels-last convolution: x [IV, Cin] on ``grid``, dy [OV, Cout] on the output
-        grid (``sgc_conv3d_wgrad_bf16x3``; ksize 2 = stride 2, no padding)."""
+        grid (``sgc_conv3d_wgrad_bf16x3``; ksize 2 = stride 2, no padding).  ``scenes`` > 1: x [scenes * IV, Cin] and dy
+        [scenes * OV, Cout] hold that many volumes one after the other and dW is their sum, formed inside the launch
+        (``sgc_conv3d_wgrad_bf16x3_batched``)."""
         self._check(x=x, dy=dy)
         self._f32(x=x, dy=dy)
         ix, iy, iz = grid
@@ -1144,13 +1160,21 @@ class TensorOps:
         og = tuple((d + 2 * pad - ksize) // stride + 1 for d in grid)
         V, Cin = x.shape
         OV, Cout = dy.shape
-        if V != ix * iy * iz or OV != og[0] * og[1] * og[2]:
+        scenes = int(scenes)
+        if scenes < 1 or V != scenes * ix * iy * iz or OV != scenes * og[0] * og[1] * og[2]:
             raise RuntimeError("conv3d_wgrad_bf16x3: inconsistent shapes")
         dw = torch.empty((ksize ** 3, Cout, Cin), dtype=torch.float32, device=x.device)
-        n = int(self.lib._dll.sgc_conv3d_wgrad_workspace_floats(ix, iy, iz, Cin, Cout, ksize, stride))
+        if scenes > 1:
+            n = int(self.lib._dll.sgc_conv3d_wgrad_batched_workspace_floats(ix, iy, iz, Cin, Cout, ksize, stride, scenes))
+        else:
+            n = int(self.lib._dll.sgc_conv3d_wgrad_workspace_floats(ix, iy, iz, Cin, Cout, ksize, stride))
         if n < 0:
             raise RuntimeError("conv3d_wgrad_bf16x3: " + self.lib.last_error())
         ws = torch.empty(n, dtype=torch.float32, device=x.device) if n > 0 else None
+        if scenes > 1:
+            self._call("sgc_conv3d_wgrad_bf16x3_batched", x, dy, dw, ix, iy, iz, Cin, Cout, ksize, stride, scenes, ws, n,
+                       _meta=dict(V=OV, Cin=Cin, Cout=Cout, taps=ksize ** 3, OV=OV))
+            return dw
         self._call("sgc_conv3d_wgrad_bf16x3", x, dy, dw, ix, iy, iz, Cin, Cout, ksize, stride, ws, n,
                    _meta=dict(V=OV, Cin=Cin, Cout=Cout, taps=ksize ** 3, OV=OV))
         return dw
@@ -1267,10 +1291,14 @@ class TensorOps:
         self._call("sgc_rows_colsum", x, out, rows, Cc, ws, n)
         return out
 
-    def _conv_workspace(self, device, ix, iy, iz, Cin, Cout, ksize, stride, transposed, bf16x3):
+    def _conv_workspace(self, device, ix, iy, iz, Cin, Cout, ksize, stride, transposed, bf16x3, scenes=1):
         """Split-K layers get a workspace so that their partial sums are added in a fixed order (bit-identical
         results from run to run); (None, 0) for layers that are not split."""
-        n = int(self.lib._dll.sgc_conv3d_workspace_floats(ix, iy, iz, Cin, Cout, ksize, stride, 1 if transposed else 0, bf16x3))
+        if scenes > 1:             # (the scene-less query is the one the CPU oracle exports too)
+            n = int(self.lib._dll.sgc_conv3d_batched_workspace_floats(ix, iy, iz, Cin, Cout, ksize, stride, 1 if transposed else 0,
+                                                                      bf16x3, int(scenes)))
+        else:
+            n = int(self.lib._dll.sgc_conv3d_workspace_floats(ix, iy, iz, Cin, Cout, ksize, stride, 1 if transposed else 0, bf16x3))
         if n <= 0:
             return None, 0
         return torch.empty(n, dtype=torch.float32, device=device), n

@@ -28,17 +28,32 @@ ap.add_argument("--level-fused", default=None, choices=["0", "1", "ab"],
                 help="plugin/voxformer.py TRAIN_LEVEL_FUSED (DESIGN.md 4.19): 0 / 1 set the switch for the run; ab alternates the two settings block "
                      "by block in this one process and reports, per setting, the median and the spread of the blocks of 10 steps and the kernel "
                      "launches of a step (all, and those not of this library); with --sites also each setting's table")
+ap.add_argument("--scenes", type=int, default=1, help="scenes per step (DESIGN.md 4.20): the voxel head runs scene by scene, neck_3d and the head on the batch")
+ap.add_argument("--scene-batch", default=None, choices=["batched", "loop", "ab"],
+                help="plugin/conv_plan.py TRAIN_SCENE_BATCH: batched / loop set the switch for the run; ab alternates, block by block in this one "
+                     "process, one scene per step, --scenes batched and --scenes loop, and reports per setting the median and the spread of the "
+                     "blocks of 10 steps")
 ap.add_argument("--glue", action="store_true", help="attribute the torch glue ops (copy / add / fill / sum / mul ...) to source lines of this package")
 args = ap.parse_args()
 w = workload(args.workload)
 torch.manual_seed(0)
 det = build_detector(model_config(w)).cuda().train()
-feats, dpt, meta = make_scene(w["n_views"], w["embed_dims"], kind=w["kind"], seed=1, device="cuda", img_hw=(256, 320))
+scenes = [make_scene(w["n_views"], w["embed_dims"], kind=w["kind"], seed=1 + b, device="cuda", img_hw=(256, 320)) for b in range(args.scenes)]
 if args.input_layout == "nhwc":         # same logical [1, N, C, H, W] tensors, channels-last in memory
     cl = lambda t: t[0].contiguous(memory_format=torch.channels_last).unsqueeze(0)   # noqa: E731
-    feats, dpt = [cl(f) for f in feats], cl(dpt)
+    scenes = [([cl(f) for f in fs], cl(d), m) for fs, d, m in scenes]
+feats, dpt, meta = scenes[0]
 feats = [f.requires_grad_(True) for f in feats]
 dpt = dpt.requires_grad_(True)
+metas = [m for _, _, m in scenes]
+if args.scenes > 1:                     # [B, N, C, H, W] maps and one img_meta per scene
+    feats_b = [torch.cat([sc[0][i] for sc in scenes]).detach().requires_grad_(True) for i in range(len(feats))]
+    dpt_b = torch.cat([sc[1] for sc in scenes]).detach().requires_grad_(True)
+else:
+    feats_b, dpt_b = feats, dpt
+if args.scene_batch in ("batched", "loop"):
+    from sgcdet_amd.plugin import conv_plan
+    conv_plan.set_train_scene_batch(args.scene_batch)
 params = [p for p in det.parameters() if p.requires_grad]
 if args.real_loss:
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
@@ -58,10 +73,19 @@ def set_level_fused(on):
 if args.level_fused in ("0", "1"):
     set_level_fused(args.level_fused == "1")
 
-def step():
+def step(batch=True):
+    """``batch`` False: one scene, whatever --scenes says (the per-scene baseline of --scene-batch ab)."""
     for p in params:
         p.grad = None
-    if args.no_neck:
+    if batch and args.scenes > 1:
+        if args.no_neck:
+            raise SystemExit("--scenes with --no-neck: the voxel head is batch 1, there is nothing to batch")
+        if args.real_loss:
+            loss = sum(det.forward_train_from_features(feats_b, metas, dpt_b, [gt_boxes] * args.scenes, [gt_labels] * args.scenes).values())
+        else:
+            r = det.forward_features(feats_b, metas, dpt_b)
+            loss = sum((t ** 2).mean() for k in ("centerness", "bbox_pred", "cls_score") for t in r[k]) + r["occ"].mean()
+    elif args.no_neck:
         import torch.nn.functional as F
         dpts = [dpt, F.interpolate(dpt, scale_factor=(1, 0.5, 0.5), mode="nearest"), F.interpolate(dpt, scale_factor=(1, 0.25, 0.25), mode="nearest")]
         vol, valid, occ = det.voxel_head(feats, meta, dpts)
@@ -157,13 +181,13 @@ def sites_table(label=""):
         print(f"  x{n:<4d} {name:28s} {where:46s} {shape}", file=sys.stderr)
 
 
-def launches_per_step():
+def launches_per_step(batch=True):
     """Launches of one step as torch.profiler sees them: every kernel; the kernels torch's own ops issue (``at::`` kernels and the BLAS /
     convolution libraries' -- the rest is this library's); the memory copies / fills the runtime issues as such."""
     from torch.profiler import profile, ProfilerActivity
     with profile(activities=[ProfilerActivity.CUDA]) as prof:
         for _ in range(2):
-            step()
+            step(batch)
         torch.cuda.synchronize()
     rows = [e for e in prof.key_averages() if not e.key.startswith("hip")]          # (the runtime's API rows count every launch again)
     mem = sum(e.count for e in rows if e.key.startswith(("Memcpy", "Memset")))
@@ -198,6 +222,31 @@ if args.level_fused == "ab":
     set_level_fused(0)
 elif args.sites:
     sites_table()
+scene_ab = None
+if args.scene_batch == "ab":
+    from sgcdet_amd.plugin import conv_plan
+    settings = [("one_scene", "batched", False), ("batched", "batched", True), ("loop", "loop", True)]
+    blocks = {name: [] for name, _, _ in settings}
+    for name, mode, batch in settings:
+        conv_plan.set_train_scene_batch(mode)
+        for _ in range(2):
+            step(batch)
+    for b in range(max(4, (args.steps + 9) // 10)):
+        for name, mode, batch in (settings if b % 2 == 0 else settings[::-1]):     # the settings alternate, and so does their order
+            conv_plan.set_train_scene_batch(mode)
+            torch.cuda.synchronize(); t = time.perf_counter()
+            for _ in range(10):
+                step(batch)
+            torch.cuda.synchronize()
+            blocks[name].append((time.perf_counter() - t) / 10 * 1e3)
+    scene_ab = dict(scenes=args.scenes)
+    for name, mode, batch in settings:
+        conv_plan.set_train_scene_batch(mode)
+        bs = sorted(blocks[name])
+        step(batch)
+        scene_ab[name] = dict(ms_per_step_median=round(bs[len(bs) // 2], 3), ms_per_step_min=round(bs[0], 3), ms_per_step_max=round(bs[-1], 3),
+                              blocks=len(bs), launches_per_step=launches_per_step(batch))
+    conv_plan.set_train_scene_batch("batched")
 if args.cprofile:
     import cProfile, pstats, io
     pr = cProfile.Profile()
@@ -216,10 +265,10 @@ if args.wgrad_layers:
     ops = ext.ops()
     calls, orig = [], ops.conv3d_wgrad_bf16x3
 
-    def spy(x, dy, grid, ksize, stride=1):
+    def spy(x, dy, grid, ksize, stride=1, scenes=1):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        out = orig(x, dy, grid, ksize, stride)
+        out = orig(x, dy, grid, ksize, stride, scenes=scenes)
         e1.record()
         calls.append((x.shape[1], dy.shape[1], tuple(grid), ksize, stride, e0, e1))
         return out
@@ -257,4 +306,5 @@ if args.glue:
 print(json.dumps(dict(workload=args.workload, ms_per_step=ms_step, ms_per_step_best_block=ms_min, loss=l, params_with_grad=f"{n_grads}/{len(params)}",
                       peak_mem_gb=round(torch.cuda.max_memory_allocated() / 2**30, 2), no_neck=args.no_neck,
                       input_layout=args.input_layout, optimizer=args.optimizer, optimizer_variant=optimizer_variant,
-                      torch_variants_ms=variants_ms, level_fused=level_ab if level_ab is not None else args.level_fused)))
+                      torch_variants_ms=variants_ms, level_fused=level_ab if level_ab is not None else args.level_fused,
+                      scenes=args.scenes, scene_batch=scene_ab if scene_ab is not None else args.scene_batch)))
