@@ -10,7 +10,8 @@ convolutions of ``include/sgcdet_amd_image.h`` likewise (``IMAGE_SIGNATURES`` /
 ``IMAGE_INTROSPECTION``); ``include/sgcdet_amd_depth_train.h`` (``DEPTH_TRAIN_SIGNATURES`` /
 ``DEPTH_TRAIN_INTROSPECTION``), ``include/sgcdet_amd_level_train.h`` (``LEVEL_TRAIN_SIGNATURES`` /
 ``LEVEL_TRAIN_INTROSPECTION``) and ``include/sgcdet_amd_scene_batch.h`` (``SCENE_BATCH_SIGNATURES`` /
-``SCENE_BATCH_INTROSPECTION``) are bound together with the training tables.  Nothing
+``SCENE_BATCH_INTROSPECTION``) and ``include/sgcdet_amd_syncbn.h`` (``SYNCBN_SIGNATURES`` / ``SYNCBN_INTROSPECTION``) are bound
+together with the training tables.  Nothing
 here touches torch; pointers are plain integers (``tensor.data_ptr()``).
 """
 import ctypes as C
@@ -164,6 +165,19 @@ SCENE_BATCH_INTROSPECTION = {
     "sgc_conv3d_wgrad_batched_workspace_floats": (C.c_int64, [_i] * 8),
 }
 
+# include/sgcdet_amd_syncbn.h: the BatchNorm passes over rows cut at the collective of SyncBatchNorm -- local statistics / global
+# apply, local sums / global apply (no CPU-oracle twin; bound with the training tables)
+SYNCBN_SIGNATURES = {
+    "sgc_bn_rows_sync_stats": [_p] * 3 + [C.c_int64, _i, _i, _p],
+    "sgc_bn_rows_sync_apply": [_p, _p, _i] + [_p] * 4 + [_f, _f] + [_p, _i] + [_p] * 4 + [_i, _i, _p],
+    "sgc_bn_rows_sync_backward_sums": [_p] * 7 + [C.c_int64, _i, _i, _p],
+    "sgc_bn_rows_sync_backward_apply": [_p] * 10 + [_i, _i, _p],
+}
+
+SYNCBN_INTROSPECTION = {}      # the workspace is sized with sgc_bn_rows_workspace_floats (INTROSPECTION)
+SYNCBN_MAX_WORLD = 1024        # == SGC_SYNCBN_MAX_WORLD
+SYNCBN_MAX_COUNT = 1 << 24     # counts travel as fp32: rows per rank and world * rows stay below it
+
 # include/sgcdet_amd_image.h: the 2-D convolutions of the image-side CNNs (no CPU-oracle twin)
 IMAGE_SIGNATURES = {
     "sgc_conv2d_nhwc_ex_bf16x3": [_p] * 7 + [_i] * 13 + [_p],
@@ -202,16 +216,19 @@ class Library:
 
     def __init__(self, path, train=False, image=False):
         """``train`` / ``image``: also bind (and require) the entry points of include/sgcdet_amd_train.h and
-        include/sgcdet_amd_depth_train.h, include/sgcdet_amd_level_train.h, include/sgcdet_amd_scene_batch.h / of
+        include/sgcdet_amd_depth_train.h, include/sgcdet_amd_level_train.h, include/sgcdet_amd_scene_batch.h,
+        include/sgcdet_amd_syncbn.h / of
         include/sgcdet_amd_image.h."""
         self.path = str(path)
         self._dll = C.CDLL(self.path)
         missing = []
         signatures = {**SIGNATURES, **(TRAIN_SIGNATURES if train else {}), **(DEPTH_TRAIN_SIGNATURES if train else {}),
                       **(LEVEL_TRAIN_SIGNATURES if train else {}), **(SCENE_BATCH_SIGNATURES if train else {}),
+                      **(SYNCBN_SIGNATURES if train else {}),
                       **(IMAGE_SIGNATURES if image else {})}
         introspection = {**INTROSPECTION, **(TRAIN_INTROSPECTION if train else {}), **(DEPTH_TRAIN_INTROSPECTION if train else {}),
                          **(LEVEL_TRAIN_INTROSPECTION if train else {}), **(SCENE_BATCH_INTROSPECTION if train else {}),
+                         **(SYNCBN_INTROSPECTION if train else {}),
                          **(IMAGE_INTROSPECTION if image else {})}
         for name, argtypes in signatures.items():
             try:

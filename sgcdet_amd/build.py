@@ -37,7 +37,7 @@ def is_stale():
     t = os.path.getmtime(LIB)
     deps = sources() + glob.glob(os.path.join(CSRC, "*.hpp")) + \
         [os.path.join(HERE, "..", "include", h) for h in ("sgcdet_amd.h", "sgcdet_amd_train.h", "sgcdet_amd_image.h", "sgcdet_amd_depth_train.h",
-                                                           "sgcdet_amd_level_train.h", "sgcdet_amd_scene_batch.h")]
+                                                           "sgcdet_amd_level_train.h", "sgcdet_amd_scene_batch.h", "sgcdet_amd_syncbn.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

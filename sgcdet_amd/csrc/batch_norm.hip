@@ -10,12 +10,15 @@
 // One set of kernels serves every entry: rows of pitch ld >= C, a tail 0 / 1 / 2.  sgc_bn_rows_forward / _backward and
 // sgc_bn_rows_act_forward / _backward are these kernels at ld == C with tails 0 / 1; sgc_bn_rows_padded_forward / _backward
 // (include/sgcdet_amd_depth_train.h: the regulation U-Nets of DepthNet_Fusion in training) pass pitch and tail through.
+// sgc_bn_rows_sync_* (include/sgcdet_amd_syncbn.h) are the same passes cut where the caller of a SyncBatchNorm runs its
+// collective: local statistics | merge of the ranks + apply, local sums | apply.
 //
 // Round 2 ran torch's channels-last batch-norm kernels here: 43 us (statistics) + 52 us (backward reduction) per layer for
 // 26 MB tensors, 1.5 ms of a 25 ms training step.  These are plain column reductions: a workgroup walks a slab of rows with
 // 16-byte loads (a thread owns 4 channels), partial results meet in a small workspace.
 #include "common.hpp"
 #include "../../include/sgcdet_amd_depth_train.h"
+#include "../../include/sgcdet_amd_syncbn.h"
 
 namespace sgc {
 
@@ -103,17 +106,16 @@ __global__ __launch_bounds__(BN_T) void bn_stats_partial_kernel(const float *__r
   }
 }
 
-// merge the slabs; batch statistics, running statistics (nn.BatchNorm: unbiased variance), invstd.  BN_FJ lanes per channel each
-// merge a contiguous run of slabs in order, lane 0 merges the BN_FJ results in lane order: a fixed tree, the same bits every run.
+// merge the slabs of one channel.  BN_FJ lanes per channel each merge a contiguous run of slabs in order, lane 0 merges the BN_FJ
+// results in lane order: a fixed tree, the same bits every run.  True on the lane that then holds channel c's (count, mean, M2)
 constexpr int BN_FJ = 8, BN_FC = BN_T / BN_FJ;       // lanes per channel, channels per workgroup
-__global__ __launch_bounds__(BN_T) void bn_stats_final_kernel(const float *__restrict__ ws, int G, int rows, int rows_per_slab, int C, float eps,
-                                                              float momentum, float *__restrict__ mean_out, float *__restrict__ invstd_out,
-                                                              float *__restrict__ running_mean, float *__restrict__ running_var) {
+__device__ __forceinline__ bool bn_merge_slabs(const float *__restrict__ ws, int G, int rows, int rows_per_slab, int C, int &c, float &na, float &ma,
+                                               float &Ma) {
   __shared__ float part[BN_FJ][BN_FC][3];
   const int cl = threadIdx.x % BN_FC, j = threadIdx.x / BN_FC;
-  const int c = blockIdx.x * BN_FC + cl;
+  c = blockIdx.x * BN_FC + cl;
   const int per = (G + BN_FJ - 1) / BN_FJ;
-  float na = 0.f, ma = 0.f, Ma = 0.f;
+  na = 0.f, ma = 0.f, Ma = 0.f;
   if (c < C) {
     for (int g = j * per; g < min(G, (j + 1) * per); ++g) {
       const int cnt = min(rows, (g + 1) * rows_per_slab) - g * rows_per_slab;
@@ -123,13 +125,60 @@ __global__ __launch_bounds__(BN_T) void bn_stats_final_kernel(const float *__res
   }
   part[j][cl][0] = na; part[j][cl][1] = ma; part[j][cl][2] = Ma;
   __syncthreads();
-  if (j != 0 || c >= C) return;
+  if (j != 0 || c >= C) return false;
   for (int l = 1; l < BN_FJ; ++l) chan_merge(na, ma, Ma, part[l][cl][0], part[l][cl][1], part[l][cl][2]);
+  return true;
+}
+
+// batch statistics, running statistics (nn.BatchNorm: unbiased variance), invstd of the merged slabs
+__global__ __launch_bounds__(BN_T) void bn_stats_final_kernel(const float *__restrict__ ws, int G, int rows, int rows_per_slab, int C, float eps,
+                                                              float momentum, float *__restrict__ mean_out, float *__restrict__ invstd_out,
+                                                              float *__restrict__ running_mean, float *__restrict__ running_var) {
+  int c;
+  float na, ma, Ma;
+  if (!bn_merge_slabs(ws, G, rows, rows_per_slab, C, c, na, ma, Ma)) return;
   const float var = Ma / (float)rows;
   mean_out[c] = ma;
   invstd_out[c] = 1.0f / sqrtf(var + eps);
   if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * ma;
   if (running_var) running_var[c] = (1.f - momentum) * running_var[c] + momentum * (rows > 1 ? Ma / (float)(rows - 1) : var);
+}
+
+// ---- the seam of SyncBatchNorm (include/sgcdet_amd_syncbn.h): local | collective | global ---------------------------
+// The local half of the forward ends where bn_stats_final_kernel would turn (mean, M2) into a variance: this rank's merged slabs
+// leave as packed [mean (C) | M2 (C) | count (1)], M2 the SUM of squared deviations, so that the ranks meet in the Chan step the
+// slabs met in
+__global__ __launch_bounds__(BN_T) void bn_sync_stats_final_kernel(const float *__restrict__ ws, int G, int rows, int rows_per_slab, int C,
+                                                                   float *__restrict__ packed) {
+  int c;
+  float na, ma, Ma;
+  if (!bn_merge_slabs(ws, G, rows, rows_per_slab, C, c, na, ma, Ma)) return;
+  packed[c] = ma;
+  packed[C + c] = Ma;
+  if (c == 0) packed[2 * C] = (float)rows;
+}
+
+// The global half: the ranks of gathered [world, 2C + 1] merged in rank order (every rank computes the same bits; one rank is the
+// identity: its own mean and M2 pass through untouched), then what bn_stats_final_kernel does with rows -> the total count, which
+// stays on the device as 1 / N for the backward.  One thread per channel: the loop is world long
+__global__ __launch_bounds__(BN_T) void bn_sync_merge_kernel(const float *__restrict__ gathered, int world, int C, float eps, float momentum,
+                                                             float *__restrict__ mean_out, float *__restrict__ invstd_out,
+                                                             float *__restrict__ inv_count_out, float *__restrict__ running_mean,
+                                                             float *__restrict__ running_var) {
+  const int c = blockIdx.x * BN_T + threadIdx.x;
+  if (c >= C) return;
+  const int64_t pitch = 2 * (int64_t)C + 1;
+  float na = gathered[2 * C], ma = gathered[c], Ma = gathered[C + c];
+  for (int r = 1; r < world; ++r) {
+    const float *q = gathered + r * pitch;
+    chan_merge(na, ma, Ma, q[2 * C], q[c], q[C + c]);
+  }
+  const float var = Ma / na;
+  mean_out[c] = ma;
+  invstd_out[c] = 1.0f / sqrtf(var + eps);
+  if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * ma;
+  if (running_var) running_var[c] = (1.f - momentum) * running_var[c] + momentum * (na > 1.f ? Ma / (na - 1.f) : var);
+  if (c == 0) inv_count_out[0] = 1.0f / na;
 }
 
 // the normalisation with its elementwise tail (round 5): the ResBlock tail `relu(norm2(conv2) + identity)` and the `relu(norm(conv))`
@@ -247,12 +296,11 @@ __global__ __launch_bounds__(BN_T) void bn_bwd_final_kernel(const float *__restr
 // dres: the gradient of the added identity -- behind the gate for tails 0 / 1 (the add sits in front of the ReLU; tail 0 has no
 // gate: the incoming gradient), the incoming gradient itself for tail 2 (the add sits behind it)
 template <int TAIL>
-__global__ __launch_bounds__(BN_T) void bn_bwd_apply_kernel(const float *__restrict__ x, const float *__restrict__ dy, const float *__restrict__ mean,
-                                                            const float *__restrict__ invstd, const float *__restrict__ w,
-                                                            const float *__restrict__ b, const float *__restrict__ dw,
-                                                            const float *__restrict__ db, float *__restrict__ dx, int64_t total4, int C4, int ld4,
-                                                            float inv_rows, const float *__restrict__ y_or_null,
-                                                            float *__restrict__ dres_or_null) {
+__device__ __forceinline__ void bn_bwd_apply_rows(const float *__restrict__ x, const float *__restrict__ dy, const float *__restrict__ mean,
+                                                  const float *__restrict__ invstd, const float *__restrict__ w, const float *__restrict__ b,
+                                                  const float *__restrict__ dw, const float *__restrict__ db, float *__restrict__ dx,
+                                                  int64_t total4, int C4, int ld4, float inv_rows, const float *__restrict__ y_or_null,
+                                                  float *__restrict__ dres_or_null) {
   for (int64_t i = (int64_t)blockIdx.x * BN_T + threadIdx.x; i < total4; i += (int64_t)gridDim.x * BN_T) {
     const int c4 = (int)(i % ld4);
     float4 *dx4 = reinterpret_cast<float4 *>(dx) + i;
@@ -274,6 +322,27 @@ __global__ __launch_bounds__(BN_T) void bn_bwd_apply_kernel(const float *__restr
     *dx4 = make_float4(bn_dx(v4.x, g4.x, m4.x, i4.x, w4.x, db4.x, dw4.x, inv_rows), bn_dx(v4.y, g4.y, m4.y, i4.y, w4.y, db4.y, dw4.y, inv_rows),
                        bn_dx(v4.z, g4.z, m4.z, i4.z, w4.z, db4.z, dw4.z, inv_rows), bn_dx(v4.w, g4.w, m4.w, i4.w, w4.w, db4.w, dw4.w, inv_rows));
   }
+}
+
+template <int TAIL>
+__global__ __launch_bounds__(BN_T) void bn_bwd_apply_kernel(const float *__restrict__ x, const float *__restrict__ dy, const float *__restrict__ mean,
+                                                            const float *__restrict__ invstd, const float *__restrict__ w,
+                                                            const float *__restrict__ b, const float *__restrict__ dw,
+                                                            const float *__restrict__ db, float *__restrict__ dx, int64_t total4, int C4, int ld4,
+                                                            float inv_rows, const float *__restrict__ y_or_null,
+                                                            float *__restrict__ dres_or_null) {
+  bn_bwd_apply_rows<TAIL>(x, dy, mean, invstd, w, b, dw, db, dx, total4, C4, ld4, inv_rows, y_or_null, dres_or_null);
+}
+
+// the same pass behind the all-reduce of SyncBatchNorm: sums = [sum g | sum g * xhat] over the rows of ALL ranks, and 1 / N of all
+// ranks read from device memory (bn_sync_merge_kernel left it there: no host read-back between the passes).  Dense rows, tails 0 / 1
+template <int TAIL>
+__global__ __launch_bounds__(BN_T) void bn_sync_bwd_apply_kernel(const float *__restrict__ x, const float *__restrict__ dy,
+                                                                 const float *__restrict__ mean, const float *__restrict__ invstd,
+                                                                 const float *__restrict__ w, const float *__restrict__ sums,
+                                                                 const float *__restrict__ inv_count, float *__restrict__ dx, int64_t total4,
+                                                                 int C4, const float *__restrict__ y_or_null, float *__restrict__ dres_or_null) {
+  bn_bwd_apply_rows<TAIL>(x, dy, mean, invstd, w, nullptr, sums + C4 * 4, sums, dx, total4, C4, C4, inv_count[0], y_or_null, dres_or_null);
 }
 
 static void bn_geometry(int rows, int &G, int &rows_per_slab) {
@@ -415,4 +484,101 @@ extern "C" int sgc_bn_rows_padded_backward(const float *x, const float *dy, cons
                                            int ld, sgc_stream_t stream) {
   return bn_backward_launch("sgc_bn_rows_padded_backward", x, dy, y_or_null, mean, invstd, weight, bias_or_null, dx, dweight, dbias,
                             dresidual_or_null, tail, workspace, workspace_floats, rows, C, ld, stream);
+}
+
+// ---- SyncBatchNorm (include/sgcdet_amd_syncbn.h): the two launchers above cut at the collective ------------------------------------
+static int bn_sync_check(const char *who, int rows, int C) {
+  int rc = bn_check(who, rows, C, C, 0);
+  if (rc) return rc;
+  if (rows >= (1 << 24)) return set_error(SGC_EUNSUP, "%s: counts travel as fp32: rows = %d is not below 2^24", who, rows);
+  return SGC_OK;
+}
+
+static int bn_apply_grid(int64_t total4) { return (int)((total4 + BN_T - 1) / BN_T < 4096 ? (total4 + BN_T - 1) / BN_T : 4096); }
+
+extern "C" int sgc_bn_rows_sync_stats(const float *x, float *stats, float *workspace, int64_t workspace_floats, int rows, int C,
+                                      sgc_stream_t stream) {
+  const char *who = "sgc_bn_rows_sync_stats";
+  if (!x || !stats || !workspace) return set_error(SGC_EINVAL, "%s: null pointer", who);
+  int rc = bn_sync_check(who, rows, C);
+  if (rc) return rc;
+  if ((uintptr_t)x & 15) return set_error(SGC_EINVAL, "%s: pointers must be 16-byte aligned", who);
+  int G, rps;
+  bn_geometry(rows, G, rps);
+  if (workspace_floats < (int64_t)G * 2 * C) return set_error(SGC_EINVAL, "%s: workspace too small", who);
+  hipStream_t st = (hipStream_t)stream;
+  const int C4 = C / 4, CG = C4 < BN_T ? C4 : BN_T, RL = BN_T / CG;
+  const size_t smem = (size_t)RL * CG * 4 * 3 * sizeof(float);
+  hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(G), dim3(BN_T), smem, st, x, workspace, rows, C, C, rps);
+  rc = check_launch("bn_stats_partial_kernel");
+  if (rc) return rc;
+  hipLaunchKernelGGL(bn_sync_stats_final_kernel, dim3(ceil_div(C, BN_FC)), dim3(BN_T), 0, st, (const float *)workspace, G, rows, rps, C, stats);
+  return check_launch("bn_sync_stats_final_kernel");
+}
+
+extern "C" int sgc_bn_rows_sync_apply(const float *x, const float *gathered, int world, const float *weight, const float *bias,
+                                      float *running_mean_or_null, float *running_var_or_null, float momentum, float eps,
+                                      const float *residual_or_null, int relu, float *y, float *mean_out, float *invstd_out,
+                                      float *inv_count_out, int rows, int C, sgc_stream_t stream) {
+  const char *who = "sgc_bn_rows_sync_apply";
+  if (!x || !gathered || !weight || !bias || !y || !mean_out || !invstd_out || !inv_count_out) return set_error(SGC_EINVAL, "%s: null pointer", who);
+  int rc = bn_sync_check(who, rows, C);
+  if (rc) return rc;
+  if (world < 1 || world > SGC_SYNCBN_MAX_WORLD) return set_error(SGC_EUNSUP, "%s: world = %d outside 1 .. %d", who, world, SGC_SYNCBN_MAX_WORLD);
+  if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)residual_or_null | (uintptr_t)weight | (uintptr_t)bias | (uintptr_t)mean_out |
+       (uintptr_t)invstd_out) & 15)
+    return set_error(SGC_EINVAL, "%s: pointers must be 16-byte aligned", who);
+  if (((uintptr_t)gathered | (uintptr_t)inv_count_out) & 3) return set_error(SGC_EINVAL, "%s: gathered / inv_count_out must be 4-byte aligned", who);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(bn_sync_merge_kernel, dim3(ceil_div(C, BN_T)), dim3(BN_T), 0, st, gathered, world, C, eps, momentum, mean_out, invstd_out,
+                     inv_count_out, running_mean_or_null, running_var_or_null);
+  rc = check_launch("bn_sync_merge_kernel");
+  if (rc) return rc;
+  const int64_t total4 = (int64_t)rows * (C / 4);
+  hipLaunchKernelGGL(bn_apply_kernel, dim3(bn_apply_grid(total4)), dim3(BN_T), 0, st, reinterpret_cast<const float4 *>(x), (const float *)mean_out,
+                     (const float *)invstd_out, weight, bias, reinterpret_cast<float4 *>(y), total4, C / 4, C / 4,
+                     reinterpret_cast<const float4 *>(residual_or_null), relu ? 1 : 0);
+  return check_launch("bn_apply_kernel");
+}
+
+extern "C" int sgc_bn_rows_sync_backward_sums(const float *x, const float *dy, const float *y_relu_or_null, const float *mean,
+                                              const float *invstd, float *sums, float *workspace, int64_t workspace_floats, int rows, int C,
+                                              sgc_stream_t stream) {
+  const char *who = "sgc_bn_rows_sync_backward_sums";
+  if (!x || !dy || !mean || !invstd || !sums || !workspace) return set_error(SGC_EINVAL, "%s: null pointer", who);
+  int rc = bn_sync_check(who, rows, C);
+  if (rc) return rc;
+  if (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)y_relu_or_null | (uintptr_t)mean | (uintptr_t)invstd | (uintptr_t)sums) & 15)
+    return set_error(SGC_EINVAL, "%s: pointers must be 16-byte aligned", who);
+  int G, rps;
+  bn_geometry(rows, G, rps);
+  if (workspace_floats < (int64_t)G * 2 * C) return set_error(SGC_EINVAL, "%s: workspace too small", who);
+  hipStream_t st = (hipStream_t)stream;
+  const int C4 = C / 4, CG = C4 < BN_T ? C4 : BN_T, RL = BN_T / CG;
+  const size_t smem = (size_t)RL * CG * 4 * 2 * sizeof(float);
+  const auto partial = y_relu_or_null ? bn_bwd_partial_kernel<1> : bn_bwd_partial_kernel<0>;
+  hipLaunchKernelGGL(partial, dim3(G), dim3(BN_T), smem, st, x, dy, mean, invstd, (const float *)nullptr, (const float *)nullptr, workspace, rows, C, C,
+                     rps, y_relu_or_null);
+  rc = check_launch("bn_bwd_partial_kernel");
+  if (rc) return rc;
+  hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(ceil_div(C, BN_FC)), dim3(BN_T), 0, st, (const float *)workspace, G, C, sums + C, sums);
+  return check_launch("bn_bwd_final_kernel");
+}
+
+extern "C" int sgc_bn_rows_sync_backward_apply(const float *x, const float *dy, const float *y_relu_or_null, const float *mean,
+                                               const float *invstd, const float *weight, const float *sums, const float *inv_count, float *dx,
+                                               float *dresidual_or_null, int rows, int C, sgc_stream_t stream) {
+  const char *who = "sgc_bn_rows_sync_backward_apply";
+  if (!x || !dy || !mean || !invstd || !weight || !sums || !inv_count || !dx) return set_error(SGC_EINVAL, "%s: null pointer", who);
+  int rc = bn_sync_check(who, rows, C);
+  if (rc) return rc;
+  if (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx | (uintptr_t)y_relu_or_null | (uintptr_t)dresidual_or_null | (uintptr_t)mean |
+       (uintptr_t)invstd | (uintptr_t)weight | (uintptr_t)sums) & 15)
+    return set_error(SGC_EINVAL, "%s: pointers must be 16-byte aligned", who);
+  if ((uintptr_t)inv_count & 3) return set_error(SGC_EINVAL, "%s: inv_count must be 4-byte aligned", who);
+  const int64_t total4 = (int64_t)rows * (C / 4);
+  const auto apply = y_relu_or_null ? bn_sync_bwd_apply_kernel<1> : bn_sync_bwd_apply_kernel<0>;
+  hipLaunchKernelGGL(apply, dim3(bn_apply_grid(total4)), dim3(BN_T), 0, (hipStream_t)stream, x, dy, mean, invstd, weight, sums, inv_count, dx, total4,
+                     C / 4, y_relu_or_null, dresidual_or_null);
+  return check_launch("bn_sync_bwd_apply_kernel");
 }

@@ -686,6 +686,78 @@ class BatchNormRowsFunction(Function):
         return dx, dw, db, None, None, None, None, dres, None, None
 
 
+def _dist_on():
+    import torch.distributed as dist
+    return dist.is_available() and dist.is_initialized()
+
+
+def _sync_world(group):
+    import torch.distributed as dist
+    return dist.get_world_size(group) if _dist_on() else 1
+
+
+class SyncBatchNormRowsFunction(Function):
+    """Training-mode ``dist.SyncBatchNorm3d`` on channels-last rows [rows, C]: ``BatchNormRowsFunction``'s passes cut at the seam
+    between this rank's rows and the rows of all ranks (include/sgcdet_amd_syncbn.h).
+
+    forward   ``bn_rows_sync_stats`` -> ONE all-gather of [mean | M2 | count] (2C + 1 floats) -> ``bn_rows_sync_apply`` (ranks merged
+              in rank order on the device: the same bits on every rank; running statistics over the rows of all ranks; the tail
+              ``relu?(bn + residual?)`` in the pass)
+    backward  ``bn_rows_sync_backward_sums`` -> ONE all-reduce of [sum g | sum g * xhat] (2C floats) ->
+              ``bn_rows_sync_backward_apply`` (1 / N_total read from device memory)
+
+    No value is read back to the host between a pass's entry and exit.  ``dweight`` / ``dbias`` are this rank's LOCAL sums: the step's
+    gradient all-reduce averages them like every other parameter gradient (``dist._SyncBatchNormFn`` documents the same).  With no
+    initialised process group ``world`` is 1 and no collective is called; an initialised group of one rank runs both collectives
+    (a copy and the identity).  Either way one rank's results are bit for bit ``BatchNormRowsFunction``'s.  ``tail`` is 0 or 1;
+    ``group`` the process group (None: the default group)."""
+
+    @staticmethod
+    def forward(ctx, rows, weight, bias, running_mean, running_var, momentum, eps, residual=None, tail=0, group=None):
+        ops = ext.ops()
+        tail = int(tail)
+        if tail not in (0, 1):
+            raise ValueError("SyncBatchNormRowsFunction: tail is 0 or 1")
+        x = rows.contiguous()
+        res = None if residual is None else residual.detach().contiguous()
+        w, b = weight.detach().contiguous(), bias.detach().contiguous()
+        world, collective = _sync_world(group), _dist_on()
+        stats = ops.bn_rows_sync_stats(x)
+        gathered = stats
+        if collective:
+            import torch.distributed as dist
+            gathered = torch.empty((world, stats.numel()), dtype=stats.dtype, device=stats.device)
+            dist.all_gather_into_tensor(gathered, stats, group=group)
+        y, mean, invstd, inv_count = ops.bn_rows_sync_apply(x, gathered, w, b, running_mean, running_var, momentum, eps, residual=res,
+                                                            relu=bool(tail))
+        ctx.tail, ctx.has_res, ctx.group, ctx.collective = tail, residual is not None, group, collective
+        ctx.save_for_backward(x, mean, invstd, inv_count, w, *((y,) if tail == 1 else ()))
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_y):
+        ops = ext.ops()
+        saved = ctx.saved_tensors
+        x, mean, invstd, inv_count, w = saved[:5]
+        y_relu = saved[5] if ctx.tail == 1 else None
+        g = grad_y.float().contiguous()
+        want_res = ctx.has_res and ctx.needs_input_grad[7]
+        sums = ops.bn_rows_sync_backward_sums(x, g, mean, invstd, y_relu=y_relu)
+        local = sums
+        if ctx.collective:
+            import torch.distributed as dist
+            local = sums.clone()                           # dbias | dweight stay this rank's sums
+            dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=ctx.group)
+        C = w.numel()
+        # no mask (tail 0): the identity's gradient IS the incoming gradient
+        dx, dres = ops.bn_rows_sync_backward_apply(x, g, mean, invstd, w, sums, inv_count, y_relu=y_relu,
+                                                   want_dresidual=want_res and ctx.tail == 1)
+        if want_res and ctx.tail == 0:
+            dres = g
+        return dx, local[C:], local[:C], None, None, None, None, dres, None, None
+
+
 def _padded_planes(weight, **form):
     """The parameter's planes with both channel counts zero-padded to multiples of 32 (the K tile and the rows' pitch)."""
     return _TRAIN_PLANES.get(weight, pad_rows=32, pad_cols=32, **form)

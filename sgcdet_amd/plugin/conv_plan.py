@@ -279,6 +279,9 @@ class BiasConv2d:
 TRAIN_CONV = os.environ.get("SGC_TRAIN_CONV", "hip")
 BN_ON_HIP = os.environ.get("SGC_BN_HIP", "1") != "0"      # training-mode BatchNorm of the neck on sgc_bn_rows_* (0: torch's kernels)
 BN_FUSE_TAIL = os.environ.get("SGC_BN_FUSE_TAIL", "1") != "0"   # `+ identity` / ReLU behind a BatchNorm inside its passes (0: torch ops, A/B)
+# OPT-IN (env SGC_SYNCBN_ROWS_HIP=1): a training-mode dist.SyncBatchNorm3d of the neck on the sgc_bn_rows_sync_* kernels with the fused
+# tail, one collective per pass (functions.SyncBatchNormRowsFunction); 0: the torch formulation on the NCDHW view
+SYNCBN_ROWS_HIP = os.environ.get("SGC_SYNCBN_ROWS_HIP", "0") == "1"
 # a batch of scenes through a training convolution: "batched" = one launch per pass on the `_batched` entries, the
 # weight gradient summed over the scenes inside its kernel; "loop" = the scene-less entries scene by scene (B launches per pass, B
 # weight gradients added by autograd) around the same joint norm -- the timing baseline and a second checker
@@ -384,6 +387,25 @@ def _residual_fits(residual, rows):
     return residual is None or (residual.dtype == torch.float32 and residual.shape == rows.shape)
 
 
+def syncbn_counts_fit(rows, world):
+    """The row counts of a SyncBatchNorm travel between the ranks as fp32: exact while this rank's count and the total stay below
+    2^24 (the total assumes ranks of equal size, the reference's one scene per rank); the merge kernel's loop bounds ``world``."""
+    from .. import _abi
+    return 0 < rows < _abi.SYNCBN_MAX_COUNT and world * rows < _abi.SYNCBN_MAX_COUNT and 1 <= world <= _abi.SYNCBN_MAX_WORLD
+
+
+def _syncbn_on_kernels(bn, rows):
+    """May this norm run on ``sgc_bn_rows_sync_*``?  Opted in, a training-mode ``dist.SyncBatchNorm3d`` with a momentum and affine
+    parameters, on the HIP training path, over CUDA fp32 rows of a width the 16-byte loads accept, counts that fp32 holds."""
+    if not SYNCBN_ROWS_HIP:
+        return False
+    from .. import dist as sgc_dist
+    from ..functions import _sync_world
+    return (type(bn) is sgc_dist.SyncBatchNorm3d and bn.training and bn.momentum is not None and bn.weight is not None and bn.bias is not None
+            and TRAIN_CONV == "hip" and BN_ON_HIP and rows.is_cuda and rows.dtype == torch.float32 and rows.shape[1] % 4 == 0
+            and syncbn_counts_fit(rows.shape[0], _sync_world(bn.process_group)))
+
+
 def _bn_function(bn, rows, momentum, residual, tail, channels=None):
     from ..functions import BatchNormRowsFunction
     track = bn.training and bn.track_running_stats
@@ -395,7 +417,8 @@ def bn_rows(bn, rows, grid, residual=None, relu=False, image=False, channels=Non
     """A BatchNorm3d-like module on channels-last rows [V, C], optionally followed by ``+ residual`` and ``relu`` (the tails of the
     neck's blocks; on the HIP path they run inside the normalisation passes).  ``nn.BatchNorm3d`` over [1, C, X, Y, Z] is the
     statistics of the V rows per channel, i.e. ``F.batch_norm`` on the [V, C] matrix (same running-statistics update); any other
-    module (SyncBatchNorm3d, GroupNorm ...) gets the 5-D channels-last view.  ``nn.BatchNorm2d`` over [N, C, H, W] is the same
+    module (SyncBatchNorm3d, GroupNorm ...) gets the 5-D channels-last view -- but for a training-mode ``dist.SyncBatchNorm3d`` under
+    ``SYNCBN_ROWS_HIP`` (opt-in), which takes ``SyncBatchNormRowsFunction`` on the rows with the same fused tail.  ``nn.BatchNorm2d`` over [N, C, H, W] is the same
     statistics of the N * H * W rows (``grid`` = (N, H, W)) and takes the same branch; a 2-D norm of any other type
     (``SyncBatchNorm`` ...) gets the 4-D NCHW view of the rows.
 
@@ -420,6 +443,14 @@ def bn_rows(bn, rows, grid, residual=None, relu=False, image=False, channels=Non
         return tail(torch.nn.functional.batch_norm(rows, bn.running_mean if not bn.training or bn.track_running_stats else None,
                                                    bn.running_var if not bn.training or bn.track_running_stats else None,
                                                    bn.weight, bn.bias, use_batch, momentum, bn.eps))
+    if not image and _syncbn_on_kernels(bn, rows):
+        from ..functions import SyncBatchNormRowsFunction
+        if bn.num_batches_tracked is not None:                 # as SyncBatchNorm3d.forward counts the batch
+            bn.num_batches_tracked.add_(1)
+        fuse = BN_FUSE_TAIL and _residual_fits(residual, rows)
+        y = SyncBatchNormRowsFunction.apply(rows, bn.weight, bn.bias, bn.running_mean, bn.running_var, float(bn.momentum), float(bn.eps),
+                                            residual if fuse else None, bool(relu and fuse), bn.process_group)
+        return y if fuse else tail(y)
     if image:
         y = bn(rows.view(grid[0], grid[1], grid[2], rows.shape[1]).permute(0, 3, 1, 2))
         return tail(y.permute(0, 2, 3, 1).reshape(rows.shape[0], rows.shape[1]))

@@ -1393,6 +1393,71 @@ class TensorOps:
         recomputes its gate from x).  Padding columns of dx and dresidual are zero."""
         return self._bn_rows_bwd("bn_rows_padded_backward", True, x, dy, mean, invstd, weight, bias, y, tail, want_dresidual)
 
+    # SyncBatchNorm on the same passes (include/sgcdet_amd_syncbn.h, DESIGN.md 4.21): the caller runs one collective between the
+    # two calls of a pass; none of the four reads a value back to the host
+    def _bn_sync_ws(self, x, Cc):
+        n = int(self.lib._dll.sgc_bn_rows_workspace_floats(x.shape[0], Cc))
+        return torch.empty(max(n, 4), dtype=torch.float32, device=x.device)
+
+    def bn_rows_sync_stats(self, x):
+        """x [rows, C] -> stats [2C + 1] = [mean | M2 (sum of squared deviations) | count] of this rank's rows
+        (``sgc_bn_rows_sync_stats``): what a rank contributes to the all-gather."""
+        self._check(x=x)
+        self._f32(x=x)
+        rows, Cc = x.shape
+        stats = torch.empty(2 * Cc + 1, dtype=torch.float32, device=x.device)
+        ws = self._bn_sync_ws(x, Cc)
+        self._call("sgc_bn_rows_sync_stats", x, stats, ws, ws.numel(), rows, Cc)
+        return stats
+
+    def bn_rows_sync_apply(self, x, gathered, weight, bias, running_mean=None, running_var=None, momentum=0.1, eps=1e-5, residual=None,
+                           relu=False):
+        """``gathered`` [world, 2C + 1] (or [2C + 1] for one rank): the stats of all ranks in rank order -> (y [rows, C] =
+        relu?(bn(x) + residual?) with the statistics of all ranks, mean [C], invstd [C], inv_count [1] = 1 / N_total on the device);
+        the running statistics are updated in place as nn.BatchNorm does (``sgc_bn_rows_sync_apply``)."""
+        self._check(x=x, gathered=gathered, weight=weight, bias=bias, running_mean=running_mean, running_var=running_var, residual=residual)
+        self._f32(x=x, gathered=gathered, weight=weight, bias=bias, running_mean=running_mean, running_var=running_var, residual=residual)
+        rows, Cc = x.shape
+        world = gathered.numel() // (2 * Cc + 1)
+        if (weight.numel() != Cc or bias.numel() != Cc or world < 1 or gathered.numel() != world * (2 * Cc + 1)
+                or (residual is not None and residual.shape != x.shape)
+                or any(t is not None and t.numel() != Cc for t in (running_mean, running_var))):
+            raise RuntimeError("bn_rows_sync_apply: inconsistent shapes")
+        y = torch.empty_like(x)
+        mean = torch.empty(Cc, dtype=torch.float32, device=x.device)
+        invstd = torch.empty_like(mean)
+        inv_count = torch.empty(1, dtype=torch.float32, device=x.device)
+        self._call("sgc_bn_rows_sync_apply", x, gathered, world, weight, bias, running_mean, running_var, float(momentum), float(eps), residual,
+                   int(bool(relu)), y, mean, invstd, inv_count, rows, Cc)
+        return y, mean, invstd, inv_count
+
+    def bn_rows_sync_backward_sums(self, x, dy, mean, invstd, y_relu=None):
+        """-> sums [2C] = [sum g | sum g * xhat] over this rank's rows, g = dy masked where ``y_relu`` > 0 when given
+        (``sgc_bn_rows_sync_backward_sums``): this rank's dbias | dweight, and what it contributes to the all-reduce."""
+        self._check(x=x, dy=dy, mean=mean, invstd=invstd, y_relu=y_relu)
+        self._f32(x=x, dy=dy, mean=mean, invstd=invstd, y_relu=y_relu)
+        rows, Cc = x.shape
+        if dy.shape != x.shape or mean.numel() != Cc or invstd.numel() != Cc or (y_relu is not None and y_relu.shape != x.shape):
+            raise RuntimeError("bn_rows_sync_backward_sums: inconsistent shapes")
+        sums = torch.empty(2 * Cc, dtype=torch.float32, device=x.device)
+        ws = self._bn_sync_ws(x, Cc)
+        self._call("sgc_bn_rows_sync_backward_sums", x, dy, y_relu, mean, invstd, sums, ws, ws.numel(), rows, Cc)
+        return sums
+
+    def bn_rows_sync_backward_apply(self, x, dy, mean, invstd, weight, sums, inv_count, y_relu=None, want_dresidual=False):
+        """``sums`` [2C]: the all-reduced sums of all ranks; ``inv_count`` [1]: the device scalar of ``bn_rows_sync_apply`` ->
+        (dx [rows, C], dresidual [rows, C] | None) over this rank's rows (``sgc_bn_rows_sync_backward_apply``)."""
+        self._check(x=x, dy=dy, mean=mean, invstd=invstd, weight=weight, sums=sums, inv_count=inv_count, y_relu=y_relu)
+        self._f32(x=x, dy=dy, mean=mean, invstd=invstd, weight=weight, sums=sums, inv_count=inv_count, y_relu=y_relu)
+        rows, Cc = x.shape
+        if (dy.shape != x.shape or mean.numel() != Cc or invstd.numel() != Cc or weight.numel() != Cc or sums.numel() != 2 * Cc
+                or inv_count.numel() != 1 or (y_relu is not None and y_relu.shape != x.shape)):
+            raise RuntimeError("bn_rows_sync_backward_apply: inconsistent shapes")
+        dx = torch.empty_like(x)
+        dres = torch.empty_like(x) if want_dresidual else None
+        self._call("sgc_bn_rows_sync_backward_apply", x, dy, y_relu, mean, invstd, weight, sums, inv_count, dx, dres, rows, Cc)
+        return dx, dres
+
     def softmax_rows_backward(self, p, dp, C=None, ldg=None):
         """g = p * (dp - sum(p * dp)) over the first ``C`` columns of the rows p, dp (default: all of p's) -> g [rows, ldg] with
         zero columns from C on (``sgc_softmax_rows_backward``); ``ldg`` defaults to C."""
